@@ -1,7 +1,22 @@
 #!/usr/bin/env python3
 """Benchmark: Msamples/s of the MI355X path-tracing core on BASELINE.json's headline config.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c4|c5] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it builds the scene, renders W untimed
+and K timed frames, writes the last timed frame's records if --dump-outputs is given, and prints the
+result line (metric, value, unit, higher_is_better, dtype, ms_per_step, the workload's config, the
+scene build time and the reduce).  Everything else listed under "Printed" below -- the counting
+launch and the roofline with its PMC passes, `traced_msamples_per_s`, `weak_scaling`, `sequential`,
+the comparison scene build, `drop_in`, `cpu_baseline` -- takes runs of its own and is measured only
+with --full (where --no-pmc, --no-drop-in and --no-cpu-baseline still switch single legs off).
+
+--dump-outputs DIR writes what the timed path's last step handed its caller -- rank 0's accumulation
+records after the step's reduce -- as DIR/record_sums.npy ([pixels, 4] f64: sum X, Y, Z, weight) and
+DIR/mean_colour.npy ([pixels, 3] f64: the XYZ image those sums give), row-major pixels; frames above
+1024^2 pixels are written as a fixed, seeded sample of 2^20 pixels.  The scene, the seed and every
+step's sample indices depend on the arguments alone, so two runs with the same arguments write the
+same arrays.
 
 --gpus N > 1 runs N ranks, one process per GPU: under `python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N ...` (the driver's launch) the ranks come from the
@@ -18,12 +33,14 @@ frame: rank r renders sample indices [(step*N + r)*spp, +spp) of the same image 
 split ONE frame's 256 / 1024 / 256 spp over the N ranks (strong scaling: the metric's "1024x1024
 @256spp, 1/2/4/8 GPUs" is a fixed workload), c1 / c2 give every rank a whole frame (weak) -- then the
 per-pixel sums {X, Y, Z, weight} (32 B) are summed onto rank 0 with one RCCL reduce over xGMI inside
-the timed region (vanrijn_amd/distributed.py frame_step, the same step the gloo tests run).  At N > 1
-a split config also times every rank rendering the whole frame (`weak_scaling`, secondary), and rank 0
-runs the PMC passes on its own shard after the timed regions (`roofline`).
+the timed region (vanrijn_amd/distributed.py frame_step, the same step the gloo tests run).  With
+--full, at N > 1 a split config also times every rank rendering the whole frame (`weak_scaling`,
+secondary), and rank 0 runs the PMC passes on its own shard after the timed regions (`roofline`).
 
-Printed (rank 0, one JSON line):
+Printed (rank 0, one JSON line; `value`, `ms_per_step`, `scene_build` seconds and `reduce` always, the
+other entries below with --full):
   value       total samples of all ranks / max-over-ranks wall time of the timed steps;
+  ms_per_step that wall time / --steps, in milliseconds;
   roofline    the render kernel against its binding ceiling, from rocprofv3 PMC passes run by this
               bench itself on this build and workload (live_pmc: child processes, one counter group
               each; the committed profiles/pmc_records.json only if they fail): VALU issue (f64-heavy
@@ -64,6 +81,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 from vanrijn_amd import distributed as D  # noqa: E402
+from vanrijn_amd import records as R  # noqa: E402
 from vanrijn_amd import scenes  # noqa: E402
 from vanrijn_amd.render import (AccumulationBuffer, Tile, collect_launch_times, partial_render_scene,  # noqa: E402
                                 render_tile_device, stream_check_error)
@@ -467,6 +485,28 @@ def drop_in_leg(dscene, width, height, frames, threads, device):
                        "other 64 B/pixel of the 88-B AccumulationBuffer layout), vr_merge_tile on the main thread"}
 
 
+# ---------------------------------------------------------------------------- --dump-outputs
+DUMP_MAX_PIXELS = 1 << 20  # 56 B per pixel written: 58.7 MB at most
+
+
+def dump_outputs(path, state, pixels):
+    """What the timed path's last step handed its caller: the frame's accumulation records (after the
+    step's reduce, on rank 0), as path/record_sums.npy [n, 4] f64 {sum X, Y, Z, weight} and
+    path/mean_colour.npy [n, 3] f64 (their XYZ image), row-major pixels.  A frame of more than
+    DUMP_MAX_PIXELS pixels is written as that many of them, drawn once with a fixed seed (ascending)."""
+    import numpy as np
+    torch.cuda.synchronize()
+    sums, mean = R.sums(state), D.mean_colour(state)
+    if pixels > DUMP_MAX_PIXELS:
+        pick = np.sort(np.random.default_rng(SEED).choice(pixels, DUMP_MAX_PIXELS, replace=False))
+        pick = torch.from_numpy(pick).to(state.device)
+        sums, mean = sums[pick], mean[pick]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "record_sums.npy"), sums.cpu().numpy().astype(np.float64, copy=False))
+    np.save(os.path.join(path, "mean_colour.npy"), mean.cpu().numpy().astype(np.float64, copy=False))
+    progress(f"wrote {min(pixels, DUMP_MAX_PIXELS)} pixels' record sums and mean colour to {path}")
+
+
 # ---------------------------------------------------------------------------- rank launcher
 def launch_ranks(argv, n, stub=False):
     """`--gpus n` (n > 1) started without torch.distributed.run's environment: start
@@ -543,6 +583,11 @@ def main():
     ap.add_argument("--drop-in-threads", type=int, default=8)
     ap.add_argument("--no-drop-in", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 PMC passes of the roofline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: counting launch and roofline (PMC passes), "
+                         "weak-scaling and sequential regions, the comparison scene build, drop-in leg, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's records (rank 0, after the reduce) as DIR/<name>.npy")
     ap.add_argument("--streams", type=int, default=None,
                     help="frames alternate over this many streams / record buffers (2: a frame's render "
                          "overlaps the previous frame's launch tail, ordered reduce and collective); "
@@ -557,6 +602,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "RANK" not in os.environ and args.gpus > 1:  # start the ranks (nothing has touched the GPU yet)
         return launch_ranks(sys.argv[1:], args.gpus, stub=args.stub_ranks or args.one_gpu_rehearsal)
     if "RANK" in os.environ and int(os.environ.get("WORLD_SIZE", 1)) != args.gpus:
@@ -608,7 +655,7 @@ def main():
     build_s = time.perf_counter() - t_build
     build = {"rendered_tree": "host-built" if args.host_build else "device-built (VR_SCENE_DEVICE_SAH)",
              "seconds": round(build_s, 4)}
-    if not args.pmc_child:
+    if args.full and not args.pmc_child:
         t_build = time.perf_counter()
         scene.device_scene(local, device_sah=args.host_build).info()
         build["other_build_seconds"] = round(time.perf_counter() - t_build, 4)
@@ -684,19 +731,25 @@ def main():
         step(1, spp, timed=True)
         torch.cuda.synchronize()
         return
-    progress(f"scene built in {build_s:.3f} s; counting launch")
-    # counting launch (untimed): traversal counters of exactly this rank's workload
-    counts = render_tile_device(dscene, tile, H, W, spp, SEED, rank * spp, state.data_ptr(), stream.cuda_stream,
-                                counters=True, device=local)
+    progress(f"scene built in {build_s:.3f} s")
+    counts = None
+    if args.full:
+        # counting launch (untimed): traversal counters of exactly this rank's workload
+        progress("counting launch")
+        counts = render_tile_device(dscene, tile, H, W, spp, SEED, rank * spp, state.data_ptr(), stream.cuda_stream,
+                                    counters=True, device=local)
     tr = timed_region(spp, 1)
     elapsed = tr["elapsed"]
     progress(f"timed {args.steps} steps: {elapsed / args.steps * 1e3:.3f} ms/step")
+    if args.dump_outputs and rank == 0:
+        # the last timed frame's records, before another region renders into the same buffers
+        dump_outputs(args.dump_outputs, states[(args.warmup + args.steps) % nstreams], W * H)
     rccl_ms = tr["rccl_ms"]
     samples = world * args.steps * W * H * spp
     value = samples / elapsed / 1e6
     avg_kernel_s = tr["kernel_s"]
     weak = None
-    if world > 1 and cfg["split"]:
+    if args.full and world > 1 and cfg["split"]:
         # secondary: every rank renders the whole frame's spp (weak scaling), after the headline region
         wr = timed_region(cfg["spp"], 1 + 2 * (args.warmup + args.steps))
         weak = {"value": round(world * args.steps * W * H * cfg["spp"] / wr["elapsed"] / 1e6, 3),
@@ -705,7 +758,7 @@ def main():
                 "scaling": "weak"}
         progress(f"weak: {weak['ms_per_step']} ms/step")
     sequential = None
-    if nstreams > 1:
+    if args.full and nstreams > 1:
         # the same frames strictly one after another (one stream): each frame's own latency
         sr = timed_region(spp, 1 + 4 * (args.warmup + args.steps), ns=1)
         sequential = {"value": round(samples / sr["elapsed"] / 1e6, 3), "unit": "Msamples/s", "streams": 1,
@@ -741,24 +794,29 @@ def main():
                    "parallelism": f"spp-split x{world}, RCCL reduce", "streams": nstreams,
                    "pmc_key": config_key(cfg["scene"], W, H, spp)},
     }
-    # samples of 8x8 blocks whose camera rays all miss every object (block_cull_kernel) are applied
-    # as the photon {0, 0} without tracing: the records are bit-identical with VR_LAUNCH_NO_CULL
-    # (tests/test_gpu_cull.py); every sample is counted in `value`, the traced ones here
-    out["traced_msamples_per_s"] = round(world * args.steps * counts["samples"] / elapsed / 1e6, 3)
     if weak:
         out["weak_scaling"] = weak
     if sequential:
         out["sequential"] = sequential
-    pmc = None
-    if rank == 0 and not args.no_pmc:
-        # this rank's shard (at N > 1 too: the PMC child is a one-process run of the same spp)
-        child = ["--config", args.config, "--width", str(W), "--height", str(H), "--spp", str(spp),
-                 "--scene", cfg["scene"]] + (["--mesh", args.mesh] if args.mesh else []) + \
-                (["--host-build"] if args.host_build else [])
-        pmc = live_pmc(child)
-    out["roofline"] = roofline(counts, W * H, avg_kernel_s, config_key(cfg["scene"], W, H, spp), tr["passes"], pmc)
-    if world > 1:
-        out["roofline"]["shard"] = f"rank 0's {spp} spp of the {cfg['spp'] if cfg['split'] else spp * world} spp frame"
+    if args.full:
+        # samples of 8x8 blocks whose camera rays all miss every object (block_cull_kernel) are applied
+        # as the photon {0, 0} without tracing: the records are bit-identical with VR_LAUNCH_NO_CULL
+        # (tests/test_gpu_cull.py); every sample is counted in `value`, the traced ones here
+        out["traced_msamples_per_s"] = round(world * args.steps * counts["samples"] / elapsed / 1e6, 3)
+        pmc = None
+        if rank == 0 and not args.no_pmc:
+            # this rank's shard (at N > 1 too: the PMC child is a one-process run of the same spp)
+            child = ["--config", args.config, "--width", str(W), "--height", str(H), "--spp", str(spp),
+                     "--scene", cfg["scene"]] + (["--mesh", args.mesh] if args.mesh else []) + \
+                    (["--host-build"] if args.host_build else [])
+            pmc = live_pmc(child)
+        out["roofline"] = roofline(counts, W * H, avg_kernel_s, config_key(cfg["scene"], W, H, spp), tr["passes"],
+                                   pmc)
+        if world > 1:
+            out["roofline"]["shard"] = (f"rank 0's {spp} spp of the "
+                                        f"{cfg['spp'] if cfg['split'] else spp * world} spp frame")
+        out["roofline"]["reduce_kernel_ms"] = round(tr["reduce_ms"], 3)
+        out["roofline"]["frustum_culled_sample_fraction"] = round(1.0 - counts["samples"] / (W * H * spp), 4)
     out["scene_build"] = build
     # the path's one exchange: {sum X, Y, Z, weight} of every pixel, 32 B, reduced
     # onto rank 0 inside the timed step (RCCL; under torch.distributed.run also at world size 1)
@@ -768,12 +826,10 @@ def main():
     out["reduce"] = {"collective": "dist.reduce(SUM, f64) onto rank 0" if distributed else "none (one process)",
                      "bytes_per_step_per_rank": D.reduce_bytes(state) if distributed else 0,
                      "ms_per_step": round(sum(rccl_ms) / len(rccl_ms), 3) if rccl_ms else 0.0}
-    out["roofline"]["reduce_kernel_ms"] = round(tr["reduce_ms"], 3)
-    out["roofline"]["frustum_culled_sample_fraction"] = round(1.0 - counts["samples"] / (W * H * spp), 4)
-    if rank == 0 and world == 1 and not args.no_drop_in:
+    if args.full and rank == 0 and world == 1 and not args.no_drop_in:
         progress("drop-in leg")
         out["drop_in"] = drop_in_leg(dscene, W, H, args.drop_in_frames, args.drop_in_threads, local)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         ci = cpu_info()
         threads = args.cpu_threads or ci["usable"]
         progress(f"CPU baseline on {threads} threads")

@@ -32,7 +32,7 @@ def test_bench_under_torchrun_world_one(streams):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "c2", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--no-drop-in", "--streams", str(streams)] + (["--no-pmc"] if streams == 2 else [])
+           "--full", "--no-cpu-baseline", "--no-drop-in", "--streams", str(streams)] + (["--no-pmc"] if streams == 2 else [])
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -56,7 +56,7 @@ def test_bench_two_ranks_on_one_gpu():
     regions, max-over-ranks timing, rank 0's PMC passes on its shard while rank 1 waits in the final
     barrier, one JSON line."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--one-gpu-rehearsal", "--config", "c3",
-           "--width", "256", "--height", "256", "--steps", "3", "--warmup", "1"]
+           "--width", "256", "--height", "256", "--steps", "3", "--warmup", "1", "--full"]
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -12,7 +12,7 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q -p no:cacheprovider > gpur
 rc=$?; echo "gpu tests rc=$rc"; tail -5 gpurun_out/gpu_tests.log
 STEP_OK $rc || exit $rc
 
-BENCH_ARGS=${BENCH_ARGS:-"--steps 2 --warmup 1"}
+BENCH_ARGS=${BENCH_ARGS:-"--full --steps 2 --warmup 1"}
 timeout -k 10 900 python bench.py $BENCH_ARGS > gpurun_out/bench.json 2> gpurun_out/bench.err
 rc=$?; echo "bench rc=$rc"; cat gpurun_out/bench.json; tail -3 gpurun_out/bench.err
 [ $rc -eq 0 ] || exit $rc

@@ -16,7 +16,7 @@ if [ "${TESTS:-1}" = 1 ]; then
   cat "$O/smoke.log"
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 400 python bench.py --steps 20 --warmup 5 > "$O/bench_c3.json" 2> "$O/bench_c3.err" || { echo "bench rc=$?"; tail "$O/bench_c3.err"; exit 1; }
+  timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > "$O/bench_c3.json" 2> "$O/bench_c3.err" || { echo "bench rc=$?"; tail "$O/bench_c3.err"; exit 1; }
   echo bench ok
 fi
 if [ "${CONFIGS:-1}" = 1 ]; then
@@ -24,7 +24,7 @@ if [ "${CONFIGS:-1}" = 1 ]; then
     timeout -k 10 300 python bench.py --config $c --steps 20 --warmup 3 --no-cpu-baseline --no-drop-in --no-pmc \
         > "$O/bench_$c.json" 2> "$O/bench_$c.err" || { echo "$c rc=$?"; exit 1; }
   done
-  timeout -k 10 300 python bench.py --config c5 --steps 2 --no-cpu-baseline --no-drop-in > "$O/bench_c5.json" 2> "$O/bench_c5.err" || { echo "c5 rc=$?"; exit 1; }
+  timeout -k 10 300 python bench.py --full --config c5 --steps 2 --no-cpu-baseline --no-drop-in > "$O/bench_c5.json" 2> "$O/bench_c5.err" || { echo "c5 rc=$?"; exit 1; }
   echo configs ok
 fi
 if [ "${SHARDS:-1}" = 1 ]; then

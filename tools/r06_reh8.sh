@@ -7,6 +7,6 @@ O=${OUT:-gpurun_out/r06reh}
 mkdir -p "$O"
 export TMPDIR=/tmp
 for n in 4 8; do
-  timeout -k 10 500 python bench.py --gpus $n --one-gpu-rehearsal --config c3 --steps 3 --warmup 1 --no-cpu-baseline --no-drop-in > "$O/reh$n.json" 2> "$O/reh$n.err" || { echo "n=$n rc=$?"; tail -20 "$O/reh$n.err"; exit 1; }
+  timeout -k 10 500 python bench.py --full --gpus $n --one-gpu-rehearsal --config c3 --steps 3 --warmup 1 --no-cpu-baseline --no-drop-in > "$O/reh$n.json" 2> "$O/reh$n.err" || { echo "n=$n rc=$?"; tail -20 "$O/reh$n.err"; exit 1; }
   echo "n=$n ok"; cut -c1-400 "$O/reh$n.json"
 done

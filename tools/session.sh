@@ -9,7 +9,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 STEPS=${STEPS:-"tests bench prof"}
 TAG=${TAG:-cur}
-BENCH_ARGS=${BENCH_ARGS:-"--steps 5 --warmup 1"}
+BENCH_ARGS=${BENCH_ARGS:-"--full --steps 5 --warmup 1"}
 sha256sum vanrijn_amd/lib/libvanrijn_amd.so > gpurun_out/${TAG}_lib.sha256
 for s in $STEPS; do
   step=${s%%:*}; cfg=c3
@@ -23,12 +23,12 @@ for s in $STEPS; do
       timeout -k 10 300 python __graft_entry__.py smoke > gpurun_out/${TAG}_smoke.log 2>&1
       rc=$?; echo "smoke rc=$rc"; tail -2 gpurun_out/${TAG}_smoke.log ;;
     bench)
-      if [ "$cfg" = c3 ]; then args="$BENCH_ARGS"; else args="--config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-drop-in"; fi
+      if [ "$cfg" = c3 ]; then args="$BENCH_ARGS"; else args="--full --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-drop-in"; fi
       timeout -k 10 600 python bench.py $args > gpurun_out/${TAG}_bench_$cfg.json 2> gpurun_out/${TAG}_bench_$cfg.err
       rc=$?; echo "bench $cfg rc=$rc"; cut -c 1-400 gpurun_out/${TAG}_bench_$cfg.json; tail -3 gpurun_out/${TAG}_bench_$cfg.err ;;
     prof)
       timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${TAG}_prof_$cfg -o run -- \
-          python bench.py --config $cfg --steps 2 --warmup 0 --no-cpu-baseline --no-drop-in \
+          python bench.py --full --config $cfg --steps 2 --warmup 0 --no-cpu-baseline --no-drop-in \
           > gpurun_out/${TAG}_prof_bench_$cfg.json 2> gpurun_out/${TAG}_prof_$cfg.err
       rc=$?; echo "rocprof $cfg rc=$rc" ;;
     pmc)
@@ -46,7 +46,7 @@ for s in $STEPS; do
       # bench.py under torch.distributed.run at world size 1: the RCCL group, barriers, the
       # records' dist.reduce and the max-over-ranks timing that the 8-GPU runs take
       timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-          --master-port 29517 bench.py --config $cfg --gpus 1 --steps 2 --warmup 1 --no-cpu-baseline --no-drop-in \
+          --master-port 29517 bench.py --full --config $cfg --gpus 1 --steps 2 --warmup 1 --no-cpu-baseline --no-drop-in \
           > gpurun_out/${TAG}_dist_$cfg.json 2> gpurun_out/${TAG}_dist_$cfg.err
       rc=$?; echo "dist $cfg rc=$rc"; cut -c 1-300 gpurun_out/${TAG}_dist_$cfg.json; tail -3 gpurun_out/${TAG}_dist_$cfg.err ;;
     ab)
@@ -58,7 +58,7 @@ for s in $STEPS; do
       : > gpurun_out/${TAG}_benchab_$cfg.jsonl
       for r in $(seq 1 ${ROUNDS:-3}); do
         for L in $AB_LIBS; do
-          VR_LIBRARY=$L timeout -k 10 300 python bench.py --config $cfg --steps ${AB_STEPS:-10} --warmup 2 \
+          VR_LIBRARY=$L timeout -k 10 300 python bench.py --full --config $cfg --steps ${AB_STEPS:-10} --warmup 2 \
               --no-cpu-baseline --no-drop-in --no-pmc 2>> gpurun_out/${TAG}_benchab.err | \
               python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().split(chr(10))[-1]); print(json.dumps({'lib': '$L', 'ms_per_step': d['ms_per_step'], 'kernel_ms': d['roofline']['kernel_ms'], 'reduce_ms': d['roofline'].get('reduce_kernel_ms'), 'value': d['value']}))" \
               >> gpurun_out/${TAG}_benchab_$cfg.jsonl
