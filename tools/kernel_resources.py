@@ -1,5 +1,5 @@
 """VGPR / SGPR / scratch / LDS of the render-kernel instantiations (analysis aid).
-    python tools/kernel_resources.py [extra hipcc flags]"""
+    python tools/kernel_resources.py [other/vr_render.hip] [extra hipcc flags]"""
 import os
 import re
 import subprocess
@@ -11,9 +11,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def main():
     out = os.path.join(tempfile.mkdtemp(), "render.s")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
-                           "-ffp-contract=off", "-fno-fast-math", "--cuda-device-only", "-S"] + sys.argv[1:] +
-                          [os.path.join(ROOT, "vanrijn_amd/csrc/vr_render.hip"), "-o", out], stderr=subprocess.DEVNULL)
+    # the product build's compile flags (vanrijn_amd/build.py FLAGS): the scheduler options change registers
+    flags = subprocess.check_output([sys.executable, os.path.join(ROOT, "vanrijn_amd/build.py"), "--print-flags"],
+                                    text=True).split()
+    extra = sys.argv[1:]
+    src = os.path.join(ROOT, "vanrijn_amd/csrc/vr_render.hip")
+    if extra and extra[0].endswith(".hip"):  # another revision's source (e.g. from git archive)
+        src, extra = extra[0], extra[1:]
+    subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["--cuda-device-only", "-S"] + extra + [src, "-o", out],
+                          stderr=subprocess.DEVNULL)
     meta = open(out).read().split("amdhsa.kernels:")[1]
     for blk in re.split(r"\n  - ", meta):
         name = re.search(r"\.name:\s+(\S+)", blk)

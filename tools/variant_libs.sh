@@ -4,7 +4,8 @@
 #   bash tools/variant_libs.sh base "" split "-DVR_NODE_SPLIT_LOAD" ...
 set -eu
 cd "$(dirname "$0")/.."
-FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math"
+# the product build's compile flags (vanrijn_amd/build.py FLAGS), so a variant differs only by its own
+FLAGS=$(python3 vanrijn_amd/build.py --print-flags)
 COMMON=$(mktemp -d)
 mkdir -p abx
 for s in vr_image.hip vr_build.hip vr_host.cpp; do

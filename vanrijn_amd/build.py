@@ -45,13 +45,20 @@ def stale():
     return os.path.getmtime(os.path.abspath(__file__)) > t  # the flags changed
 
 
+def compile_flags_of():
+    """The per-source compile flags of the product build (FLAGS without the link-only -shared): the
+    A/B library scripts (tools/build_rev.sh, tools/variant_libs.sh) take them from here, so an A/B
+    library differs from the product only in what the experiment changes."""
+    return [f for f in FLAGS if f != "-shared"]
+
+
 def build(force=False, verbose=False):
     """Each source compiles to its own object in parallel (no device-side linking is needed: every
     kernel is launched from its own translation unit), then one shared-library link."""
     if not force and not stale():
         return LIB
     os.makedirs(LIB_DIR, exist_ok=True)
-    compile_flags = [f for f in FLAGS if f != "-shared"]
+    compile_flags = compile_flags_of()
     if os.environ.get("VR_TUNING") == "1":  # the occupancy-variant kernels of tools/variants.py
         compile_flags.append("-DVR_TUNING_VARIANTS")
     objs, procs = [], []
@@ -76,5 +83,8 @@ def build(force=False, verbose=False):
 
 
 if __name__ == "__main__":
+    if "--print-flags" in sys.argv:  # the compile flags on one line, for the A/B scripts; builds nothing
+        print(" ".join(compile_flags_of()))
+        sys.exit(0)
     build(force="--force" in sys.argv, verbose=True)
     print(LIB)

@@ -199,7 +199,7 @@ __global__ void fill_wide_kernel(const Node* bin, const int32_t* desc, uint64_t 
         w.pad[k] = 0;
         for (int j = 0; j < 6; ++j) {
             const double v = src >= 0 ? bin[src >> 1].box[src & 1][j] : NAN;
-            w.box[k][j] = src < 0 ? NAN : ((j & 1) ? __double2float_ru(v) : __double2float_rd(v));
+            w.bound[j][k] = src < 0 ? NAN : ((j & 1) ? __double2float_ru(v) : __double2float_rd(v));
         }
     }
     out4[i] = w;

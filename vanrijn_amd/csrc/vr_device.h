@@ -446,6 +446,61 @@ __device__ __forceinline__ void slab32_flags(const float* b, const Ray32& r, flo
     sure = d < -r.e2;
     maybe = !(d > r.e2);
 }
+// The node step's form on the per-axis Node4 layout (vr_layout.h): the three axes' slab values of
+// one child arrive already ordered -- `near` from the bound the ray meets first, `far` from the
+// other --, so the per-axis fminf / fmaxf of slab32_flags (8 of its ~22 VALU) are not needed:
+// lo = max3(near), hi = min3(far), the same difference and flags.  The root box (Bvh::root_box32)
+// stays in {min, max} pairs and keeps slab32.
+// The order is the sign bit of the f32 reciprocal Ray32::ix/iy/iz, the very multiplier of the fma
+// (node_near_offsets below): |d| <= 1, so a reciprocal is never 0, and a -0 direction gives -inf,
+// whose sign is the right one.  Soundness (tests/test_slab_order.py checks it with exact f32
+// emulation):
+//  * e2 finite: every reciprocal and every -(o * i) is finite (prepare32: ek < 1e30) and no bound of
+//    a live child is NaN, so every slab value is finite; fma(b, i, n) with i and n fixed is monotone
+//    in b (non-decreasing for i > 0, non-increasing for i < 0: a correctly rounded monotone function
+//    is monotone), hence near <= far per axis and near / far are slab32_flags' fminf / fmaxf of the
+//    pair as numbers.  They can differ from them only in the sign of a zero, which changes neither
+//    the compares nor the node step's sort key (negative ints, -0 among them, clamp to 0).  lo, hi,
+//    the flags, the cull and the visiting order are what slab32_flags gives.
+//  * e2 infinite (a huge or infinite reciprocal, or exact_only() rays): NaNs (0 * inf, inf - inf)
+//    can appear and the NaN-ignoring max3 / min3 may drop another operand than the pairwise form,
+//    so lo / hi can differ.  But sure = (d < -inf) is false and maybe = !(d > inf) is true whatever
+//    lo and hi are, and the cull thresholds carry E = inf (cull_far = +inf, cull_behind = -inf:
+//    margin_of(), vr_render.hip set_cull_far), so nothing is culled in either form: every live child
+//    is taken and sent to the exact test.  Only the visiting order, which is work and not results
+//    (DESIGN.md section 5), can differ.
+__device__ __forceinline__ void slab32_ordered(float near_x, float near_y, float near_z, float far_x, float far_y,
+                                               float far_z, float e2, float& lo, float& hi, bool& maybe, bool& sure) {
+    lo = fmaxf(fmaxf(near_x, near_y), near_z);
+    hi = fminf(fminf(far_x, far_y), far_z);
+    const float d = lo - hi;
+    sure = d < -e2;
+    maybe = !(d > e2);
+}
+// Byte offsets, within a Node4, of the quads a ray meets first on x, y and z: 32 * axis + 16 where
+// the reciprocal is negative (the max bounds come first).  The far quad is at the near offset ^ 16.
+struct NodeOrder {
+    uint32_t x, y, z;
+};
+__device__ __forceinline__ NodeOrder node_near_offsets(const Ray32& r) {
+    NodeOrder o;
+    o.x = (__float_as_uint(r.ix) >> 27) & 16u;
+    o.y = ((__float_as_uint(r.iy) >> 27) & 16u) | 32u;
+    o.z = ((__float_as_uint(r.iz) >> 27) & 16u) | 64u;
+    return o;
+}
+typedef float vr_f4 __attribute__((ext_vector_type(4)));
+// The slab values of a node's four children on one axis and side: quad = that side's four bounds,
+// children paired (0, 1) and (2, 3) per packed fma (v_pk_fma_f32), t = RN(b * i + n) as in slab32
+__device__ __forceinline__ vr_f4 slab32_quad(vr_f4 q, float i, float n) {
+    const vr_f2 a = __builtin_elementwise_fma((vr_f2){q.x, q.y}, (vr_f2){i, i}, (vr_f2){n, n});
+    const vr_f2 b = __builtin_elementwise_fma((vr_f2){q.z, q.w}, (vr_f2){i, i}, (vr_f2){n, n});
+    return (vr_f4){a.x, a.y, b.x, b.y};
+}
+// one child's {near, far} slab values on one axis (lone_walk: one child per worker), the same fma
+__device__ __forceinline__ vr_f2 slab32_pair(float b_near, float b_far, float i, float n) {
+    return __builtin_elementwise_fma((vr_f2){b_near, b_far}, (vr_f2){i, i}, (vr_f2){n, n});
+}
 
 // A triangle record in one batch of five dwordx4 loads.  Left to itself the scheduler issued the
 // last vertex's z only after the first four loads had returned (two memory round trips per

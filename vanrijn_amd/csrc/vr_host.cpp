@@ -446,7 +446,7 @@ struct WideBuilder {
             w.child[k] = out[k];
             for (int j = 0; j < 6; ++j) {
                 const double v = k < n ? box[k][j] : NAN;
-                w.box[k][j] = k < n ? ((j & 1) ? round_upper(v) : round_lower(v)) : NAN;
+                w.bound[j][k] = k < n ? ((j & 1) ? round_upper(v) : round_lower(v)) : NAN;
             }
         }
         return me;
@@ -829,7 +829,7 @@ void collapse_wide(vr_scene* s, const std::vector<vr::Node>& nodes) {
             float u[6] = {INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY};
             for (int k = 0; k < 4; ++k)
                 if (w.child[k] != vr::kEmptyChild)
-                    for (int j = 0; j < 6; ++j) u[j] = (j & 1) ? std::max(u[j], w.box[k][j]) : std::min(u[j], w.box[k][j]);
+                    for (int j = 0; j < 6; ++j) u[j] = (j & 1) ? std::max(u[j], w.bound[j][k]) : std::min(u[j], w.bound[j][k]);
             const double a = (double)(u[1] - u[0]) * (u[3] - u[2]) + (double)(u[3] - u[2]) * (u[5] - u[4]) +
                              (double)(u[5] - u[4]) * (u[1] - u[0]);
             sum += a;

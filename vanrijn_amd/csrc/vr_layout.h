@@ -36,11 +36,17 @@ static_assert(sizeof(Node) == 128, "Node must be one 128-B line");
 // the f32 interval is within its error bound of a tie; then an interior child is descended (a
 // superset box: only extra work) and a leaf child's exact f64 test runs on the triangle's own box,
 // recomputed from its vertices in the leaf round.
+// The boxes are stored per axis and side, not per child: bound[j] holds bound j of the four child
+// slots, j = 0 min x, 1 max x, 2 min y, 3 max y, 4 min z, 5 max z (lo_x[4], hi_x[4], lo_y[4], hi_y[4],
+// lo_z[4], hi_z[4]: six 16-B quads).  Which of an axis's two quads a ray meets first depends only on
+// the sign of its reciprocal direction, so the node step loads each axis's quads in the ray's order
+// (near side at 32 * axis + 16 * sign, far side at that ^ 16) and needs no per-pair min / max
+// (vr_device.h slab32_ordered).  An empty slot's six bounds are NaN.
 constexpr int32_t kEmptyChild = INT32_MIN;  // ~INT32_MAX: never a triangle (tri_count <= INT32_MAX)
 struct alignas(128) Node4 {
-    float box[4][6];   // 96 B: {min x, max x, min y, max y, min z, max z} per child
-    int32_t child[4];  // 16 B
-    int32_t pad[4];    // 16 B -> 128 B, one cache line
+    float bound[6][4];  // 96 B: [min x, max x, min y, max y, min z, max z][child slot]
+    int32_t child[4];   // 16 B
+    int32_t pad[4];     // 16 B -> 128 B, one cache line
 };
 static_assert(sizeof(Node4) == 128, "Node4 must be one 128-B line");
 

@@ -297,6 +297,7 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
     rng.reset(0);
     RayPre pre;
     Ray32 pre32;
+    NodeOrder near_off = {0u, 32u, 64u};  // the ray's near-side quads of a Node4 (set with pre32)
     Best best;
     int node = -1, sp = 0, bvh_i = 0, cur_object = 0;
     int np = 0;  // this lane's queued leaf triangles not yet tested
@@ -324,14 +325,44 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
     // kept in `best` (round 4: the nested branch form with a global load of the best triangle's rank
     // was miscompiled in some builds -- a tie's new triangle index lost to the old one -- and the
     // load was a dependent global access inside a divergent branch anyway)
-    // the triangle record of leaf link ~tri and the 4-wide node `n`
+    // the triangle record of leaf link ~tri
     auto tri_at = [&](int tri) -> const TriVerts* {
         if (BIG) return VR_TRIS + (uint32_t)tri;
         return (const TriVerts*)((const char*)VR_TRIS + (uint32_t)tri * (uint32_t)sizeof(TriVerts));
     };
-    auto node_at = [&](int n) -> const Node4& {
-        if (BIG) return VR_NODES4[(uint32_t)n];
-        return *(const Node4*)((const char*)VR_NODES4 + ((uint32_t)n << 7));
+    // Node n's six quads of bounds in a ray's order (vr_layout.h Node4; no: the ray's near-side byte
+    // offsets, each < 96): q = {near x, far x, near y, far y, near z, far z}.  Each load is the scalar
+    // base plus a 32-bit per-lane offset (node << 7 | offset; the far side that ^ 16), or the node's
+    // 64-bit address plus the offset when BIG.  As in load_tri, the empty asm needs all six values at
+    // once, so the six loads are in flight together (left alone they were issued one after another,
+    // each waiting for the one before: six memory round trips per step).
+    // c: the four child links (offset 96), in the same batch.
+    typedef int32_t vr_i4 __attribute__((ext_vector_type(4)));
+    auto load_quads = [&](int n, const NodeOrder& no, vr_f4 (&q)[6], int (&c)[4]) {
+        const char* const p = BIG ? (const char*)(VR_NODES4 + (uint32_t)n) : (const char*)VR_NODES4;
+        const uint32_t b = BIG ? 0u : (uint32_t)n << 7;
+        vr_f4 q0 = *(const vr_f4*)(p + (b | no.x)), q1 = *(const vr_f4*)(p + ((b | no.x) ^ 16u));
+        vr_f4 q2 = *(const vr_f4*)(p + (b | no.y)), q3 = *(const vr_f4*)(p + ((b | no.y) ^ 16u));
+        vr_f4 q4 = *(const vr_f4*)(p + (b | no.z)), q5 = *(const vr_f4*)(p + ((b | no.z) ^ 16u));
+        vr_i4 ch = *(const vr_i4*)(p + (size_t)b + 96);  // (the load's immediate offset)
+        asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3), "+v"(q4), "+v"(q5), "+v"(ch));
+        q[0] = q0; q[1] = q1; q[2] = q2; q[3] = q3; q[4] = q4; q[5] = q5;
+        c[0] = ch.x; c[1] = ch.y; c[2] = ch.z; c[3] = ch.w;
+    };
+    // Child slot k's six bounds {min x, max x, min y, max y, min z, max z} and its link (lone_walk: one
+    // child per worker): element k of each quad, seven loads at immediate offsets from one address.
+    // Per-lane ordered offsets as in load_quads would cost an address instruction per load on the
+    // walk's critical path (C1 +1 % against the pair layout); lone_walk orders the pairs by select
+    auto load_bounds = [&](int n, int k, float (&v)[6], int& c) {
+        const char* const p = BIG ? (const char*)(VR_NODES4 + (uint32_t)n) : (const char*)VR_NODES4;
+        const char* const a = p + (size_t)((BIG ? 0u : (uint32_t)n << 7) | ((uint32_t)k << 2));
+        float v0 = *(const float*)(a), v1 = *(const float*)(a + 16);
+        float v2 = *(const float*)(a + 32), v3 = *(const float*)(a + 48);
+        float v4 = *(const float*)(a + 64), v5 = *(const float*)(a + 80);
+        int ch = *(const int32_t*)(a + 96);
+        asm volatile("" : "+v"(v0), "+v"(v1), "+v"(v2), "+v"(v3), "+v"(v4), "+v"(v5), "+v"(ch));
+        v[0] = v0; v[1] = v1; v[2] = v2; v[3] = v3; v[4] = v4; v[5] = v5;
+        c = ch;
     };
     auto takes_hit = [&](double d, uint32_t rk) {
         const bool closer = !best.kind | (d < best.d);
@@ -509,6 +540,7 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
 #endif
         pre = prepare(Ray{pre.o, pre.d});
         pre32 = prepare32(pre, S.extent);
+        near_off = node_near_offsets(pre32);
         if (COUNT) cnt.rays++;
         best.kind = kNone;
         best.d = 0.0;
@@ -862,15 +894,19 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
             if (r < t) my = (r < first_stack) ? o_node : (int)st_node[coop_vaddr(owner, om, o_sp - 1 - (r - first_stack))];
             pos = o_sp - (t - first_stack);  // stack entries left below the taken ones
             if (my >= 0) {
-                const Node4& nd = node_at(my);
                 if (COUNT) cnt.node_visits++;
                 uint32_t xm = 0;
+                // the quads in the OWNER's ray order (the node step's form, vr_device.h slab32_ordered)
+                vr_f4 q[6];
+                load_quads(my, node_near_offsets(ry), q, c);
+                const vr_f4 tnx = slab32_quad(q[0], ry.ix, ry.nx), tfx = slab32_quad(q[1], ry.ix, ry.nx);
+                const vr_f4 tny = slab32_quad(q[2], ry.iy, ry.ny), tfy = slab32_quad(q[3], ry.iy, ry.ny);
+                const vr_f4 tnz = slab32_quad(q[4], ry.iz, ry.nz), tfz = slab32_quad(q[5], ry.iz, ry.nz);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    c[k] = nd.child[k];
                     float f, g;
                     bool maybe, sure;
-                    slab32_flags(nd.box[k], ry, f, g, maybe, sure);
+                    slab32_ordered(tnx[k], tny[k], tnz[k], tfx[k], tfy[k], tfz[k], ry.e2, f, g, maybe, sure);
                     const bool lv = c[k] != kEmptyChild;
                     if (COUNT && lv) cnt.box_tests++;
                     const bool pass = lv && maybe && !(f > cf || g < cb);
@@ -964,6 +1000,10 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
         ry.ix = p32(pre32.ix); ry.iy = p32(pre32.iy); ry.iz = p32(pre32.iz);
         ry.nx = p32(pre32.nx); ry.ny = p32(pre32.ny); ry.nz = p32(pre32.nz);
         ry.e2 = p32(pre32.e2);
+        // the owner's order of each axis's two bounds: the sign bits of its f32 reciprocals (vr_device.h
+        // slab32_ordered)
+        const bool neg_x = (__float_as_uint(ry.ix) >> 31) != 0, neg_y = (__float_as_uint(ry.iy) >> 31) != 0,
+                   neg_z = (__float_as_uint(ry.iz) >> 31) != 0;
         float cf = p32(cull_far);
         const float cb = p32(cull_behind);
         const int cobj = pi(cur_object);
@@ -1010,11 +1050,15 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
             int c = 0;
             int32_t le = 0;
             if (my >= 0) {
-                const Node4& nd = node_at(my);
-                c = nd.child[k];
                 float f, g;
                 bool maybe, sure;
-                slab32_flags(nd.box[k], ry, f, g, maybe, sure);
+                // child k's six bounds, each axis's pair in the owner's ray order
+                float v[6];
+                load_bounds(my, k, v, c);
+                const vr_f2 tx = slab32_pair(neg_x ? v[1] : v[0], neg_x ? v[0] : v[1], ry.ix, ry.nx);
+                const vr_f2 ty = slab32_pair(neg_y ? v[3] : v[2], neg_y ? v[2] : v[3], ry.iy, ry.ny);
+                const vr_f2 tz = slab32_pair(neg_z ? v[5] : v[4], neg_z ? v[4] : v[5], ry.iz, ry.nz);
+                slab32_ordered(tx.x, ty.x, tz.x, tx.y, ty.y, tz.y, ry.e2, f, g, maybe, sure);
                 const bool pass = c != kEmptyChild && maybe && !(f > cf || g < cb);
                 ih = pass && c >= 0;
                 lh = pass && c < 0;
@@ -1391,9 +1435,8 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                 }
                 if (!coop && state == kTraversing && node >= 0 && VR_ROOM) {
                     VR_MARK("node_step");
-                    // 32-bit byte offset from the scalar base (node < 2^25 unless BIG): the load's saddr form,
-                    // no 64-bit address arithmetic per step
-                    const Node4& nd = node_at(node);
+                    // 32-bit byte offsets from the scalar base (node < 2^25 unless BIG): the loads' saddr form,
+                    // no 64-bit address arithmetic per step (load_quads)
                     if (COUNT) cnt.node_visits++;
                     int c[4];
                     float f[4];
@@ -1404,12 +1447,17 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                     // test runs in the leaf round, beside the triangle test (the f32 bounds tlo / thi
                     // enclose the exact interval either way, so the f32 cull stays conservative)
                     uint32_t hm = 0, xm = 0;
+                    // the six quads in the ray's order (vr_layout.h Node4, vr_device.h slab32_ordered)
+                    vr_f4 q[6];
+                    load_quads(node, near_off, q, c);
+                    const vr_f4 tnx = slab32_quad(q[0], pre32.ix, pre32.nx), tfx = slab32_quad(q[1], pre32.ix, pre32.nx);
+                    const vr_f4 tny = slab32_quad(q[2], pre32.iy, pre32.ny), tfy = slab32_quad(q[3], pre32.iy, pre32.ny);
+                    const vr_f4 tnz = slab32_quad(q[4], pre32.iz, pre32.nz), tfz = slab32_quad(q[5], pre32.iz, pre32.nz);
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        c[k] = nd.child[k];
                         float g;
                         bool maybe, sure;
-                        slab32_flags(nd.box[k], pre32, f[k], g, maybe, sure);
+                        slab32_ordered(tnx[k], tny[k], tnz[k], tfx[k], tfy[k], tfz[k], pre32.e2, f[k], g, maybe, sure);
                         const bool live = c[k] != kEmptyChild;
                         if (COUNT && live) cnt.box_tests++;
                         const bool pass = live && maybe && !(f[k] > cull_far || g < cull_behind);
