@@ -23,6 +23,8 @@
  *     simple_random_integrator.rs:26-31) belong to the call that found them: synchronous entry
  *     points return them; the asynchronous vr_render_tile_device records them in a sticky word of
  *     its stream, returned by the next vr_stream_check_error (or timed launch) on that stream.
+ *   - The film entry points (vr_film_*, VR_HAS_FILM) were added under ABI 10: they are additions
+ *     only, so VR_ABI_VERSION did not move; probe for them with VR_HAS_FILM.
  */
 #ifndef VANRIJN_AMD_H
 #define VANRIJN_AMD_H
@@ -35,6 +37,7 @@ extern "C" {
 #endif
 
 #define VR_ABI_VERSION 10
+#define VR_HAS_FILM 1 /* the vr_film_* entry points below exist (added under ABI 10) */
 #define VR_MAX_SPECTRUM_SAMPLES 64
 #define VR_RECURSION_LIMIT 128 /* camera.rs:69 */
 
@@ -336,6 +339,62 @@ int vr_resolve_state(const double* state_host, uint64_t pixel_count, double* col
  * weight, src colour, src weight) = (c1 * w1 + c2 * w2) * (1 / (w1 + w2)); dst weight += src
  * weight.  dst's colour_sum / bias buffers are not touched (as in the reference).  Host only (ABI 4). */
 int vr_merge_tile(vr_accumulation_buffer* dst, vr_tile tile, const vr_accumulation_buffer* src);
+
+/* ---------------------------------------------------------------------------------------------
+ * Film: the reference's full-image AccumulationBuffer (accumulation_buffer.rs:6-12) as a device
+ * object, for main.rs's call pattern (main.rs:197-243): workers render 1-spp tiles, every tile is
+ * folded into the image with merge_tile, the image goes through to_image_rgb_u8 for display.  With
+ * a film the tile buffer never leaves the GPU, merge_tile runs there, and the display side reads
+ * back 3 bytes per pixel.  Added under ABI 10 (VR_HAS_FILM).
+ *
+ * Arithmetic is that of vr_render_tile followed by vr_merge_tile, bit for bit.  merge_tile is not
+ * commutative in floating point, so the merges of one film are serialised: each call is given a
+ * merge_index (consecutive from 0, in the order the calls pass the film's lock) and the film is
+ * what merging in that order gives.  A failed call may consume an index but leaves the film
+ * unchanged bit for bit.  A snapshot (read, to_image_*) contains exactly the successful merges
+ * with index < *merges_seen; later merges wait for it.  Rendering itself is not serialised: every
+ * call renders on its own call context, only merges and snapshots are ordered.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct vr_film vr_film;
+
+/* AccumulationBuffer::new (accumulation_buffer.rs:14-28) on `device`: 32 B per pixel {colour X, Y, Z,
+ * weight}, plus as much again for snapshots.  More than 2^32 pixels: VR_ERROR_UNSUPPORTED. */
+int vr_film_create(uint64_t width, uint64_t height, int32_t device, vr_film** out);
+/* Waits for the film's queued merges; NULL is allowed. */
+void vr_film_destroy(vr_film* film);
+/* Back to AccumulationBuffer::new; the merge index restarts at 0. */
+int vr_film_clear(vr_film* film);
+
+typedef struct vr_film_merge {
+    uint64_t merge_index;  /* position of this call's merge_tile in the film's merge order */
+    uint64_t first_sample; /* sample index the call rendered (the scene's pass counter for the drop-in form) */
+} vr_film_merge;
+
+/* partial_render_scene + merge_tile (main.rs:204,214-216) in one call: one sample per pixel of `tile`
+ * (full-image coordinates; height/width are the film's), seed 0x5EED0001, the sample index from the
+ * scene's pass counter exactly as vr_partial_render_scene draws it; the tile buffer never leaves the
+ * device.  Returns once the merge has run, with the call's device error if any (the film is then
+ * untouched).  Thread-safe.  `info` may be NULL. */
+int vr_film_partial_render_scene(vr_film* film, const vr_scene* scene, vr_tile tile, vr_film_merge* info);
+/* Generalised: params->spp samples, explicit seed / first_sample.  params->height / width must equal
+ * the film's and params->accumulate must be 0 (the tile buffer is always fresh, as in the reference). */
+int vr_film_render_tile(vr_film* film, const vr_scene* scene, const vr_render_params* params, vr_film_merge* info);
+/* merge_tile of caller-owned device records of `tile` (the layout of vr_render_tile_device; only the
+ * sums half is read: source colour = sum * (1 / weight), 0 where the weight is 0), e.g. the result of
+ * the cross-GPU reduce.  `stream` is the stream that produced them (NULL = the null stream); the call
+ * only enqueues work on it.  state_device must be 16-byte aligned (any hipMalloc or torch allocation is).
+ * info->first_sample is 0: the call renders nothing. */
+int vr_film_merge_state(vr_film* film, vr_tile tile, const double* state_device, void* stream, vr_film_merge* info);
+
+/* Snapshot: the five host arrays of a full-image AccumulationBuffer (out->width / height must be the
+ * film's).  colour and weight are the film; colour_sum / colour_bias / weight_bias are 0 because
+ * merge_tile never touches them (accumulation_buffer.rs:62-85).  *merges_seen = number of merge
+ * indices the snapshot contains (NULL allowed). */
+int vr_film_read(vr_film* film, vr_accumulation_buffer* out, uint64_t* merges_seen);
+/* to_image_rgb_u8(&ClampingToneMapper) of a snapshot (the bytes of vr_tone_map of its colours):
+ * 3 bytes per pixel, row-major, into host memory, or into device memory enqueued on `stream`. */
+int vr_film_to_image_rgb_u8(vr_film* film, uint8_t* rgb_host, uint64_t* merges_seen);
+int vr_film_to_image_rgb_u8_device(vr_film* film, uint8_t* rgb_device, void* stream, uint64_t* merges_seen);
 
 /* Per-(pixel, sample) records, for decision-identity checks against the oracle. */
 typedef struct vr_sample_record {

@@ -125,6 +125,10 @@ class LaunchTimes(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+class FilmMerge(C.Structure):
+    _fields_ = [("merge_index", C.c_uint64), ("first_sample", C.c_uint64)]
+
+
 class SampleRecord(C.Structure):
     _fields_ = [("wavelength", C.c_double), ("intensity", C.c_double), ("xyz", C.c_double * 3),
                 ("bounces", C.c_int32), ("flags", C.c_int32)]
@@ -162,6 +166,15 @@ SIGNATURES = {
     "vr_tone_map_device": (C.c_int, [_p, _u64, _p, _i32, _p]),
     "vr_tone_map": (C.c_int, [_p, _u64, _p, _i32]),
     "vr_write_png": (C.c_int, [C.c_char_p, _p, _u32, _u32]),
+    "vr_film_create": (C.c_int, [_u64, _u64, _i32, C.POINTER(C.c_void_p)]),
+    "vr_film_destroy": (None, [_p]),
+    "vr_film_clear": (C.c_int, [_p]),
+    "vr_film_partial_render_scene": (C.c_int, [_p, _p, TileC, C.POINTER(FilmMerge)]),
+    "vr_film_render_tile": (C.c_int, [_p, _p, C.POINTER(RenderParams), C.POINTER(FilmMerge)]),
+    "vr_film_merge_state": (C.c_int, [_p, TileC, _p, _p, C.POINTER(FilmMerge)]),
+    "vr_film_read": (C.c_int, [_p, C.POINTER(AccumulationBufferC), C.POINTER(C.c_uint64)]),
+    "vr_film_to_image_rgb_u8": (C.c_int, [_p, _p, C.POINTER(C.c_uint64)]),
+    "vr_film_to_image_rgb_u8_device": (C.c_int, [_p, _p, _p, C.POINTER(C.c_uint64)]),
     "vr_scene_set_staging_limit": (C.c_int, [_p, _u64]),
     "vr_debug_set_fault_object": (C.c_int, [_p, _i32]),
     "vr_debug_set_launch_flags": (C.c_int, [_p, _u32]),

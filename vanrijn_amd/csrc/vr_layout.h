@@ -265,6 +265,15 @@ int launch_tonemap(const double* src, int from_state, uint64_t npix, uint8_t* rg
 // out back to back (to_planar = 1: records -> planar, 0: planar -> records; colour is not read;
 // 2: records -> colour_sum only, 3 f64 per pixel)
 int launch_buffer_convert(const double* src, double* dst, uint64_t npix, int to_planar, void* stream);
+// vr_image.hip: a film (32 B per pixel {colour X, Y, Z, weight}, row-major, `film_width` pixels per row).
+// merge_tile of a tile's records (sums half, tile-row-major) into it at the tile's offset; `error`:
+// the rendering call's device error word or null -- when set, the film is left as it is.
+// launch_tonemap's from_state = 2 reads a film.
+int launch_film_merge(double* film, uint64_t film_width, uint64_t start_column, uint64_t start_row,
+                      uint64_t tile_width, uint64_t tile_height, const double* state, const int32_t* error,
+                      void* stream);
+// film -> planar [colour 3n | weight n] (the two host arrays of its AccumulationBuffer that are not 0)
+int launch_film_export(const double* film, uint64_t npix, double* planar, void* stream);
 // vr_build.hip: one mesh's BVH on the device (same nodes and leaf order as the host build)
 int device_build_bvh(const double* verts, const double* norms, uint32_t n, int32_t node_base, int32_t tri_base,
                      Node* nodes, TriVerts* tris, TriNormals* normals, uint64_t* leaf_order, double* root_box,

@@ -5,6 +5,7 @@
     Tile / TileIterator                                                     util/tile_iterator.rs:1-67
     AccumulationBuffer::to_image_rgb_u8(&ClampingToneMapper)               accumulation_buffer.rs:38-42
     ImageRgbU8 (get_colour, get_pixel_data, write_png)                      image.rs:8-66
+    Film: the full-image AccumulationBuffer of main.rs:197-243 on the GPU   (vr_film_*)
 
 Every render call goes through the C ABI into the gfx950 kernels; nothing here computes a pixel.
 """
@@ -320,6 +321,94 @@ class ImageRgbU8:
     def write_png(self, path):
         N.check(N.lib().vr_write_png(str(path).encode(), self.data.ctypes.data_as(C.c_void_p), self.get_width(),
                                      self.get_height()))
+
+
+class Film:
+    """The reference's full-image AccumulationBuffer resident on one GPU (vr_film): main.rs:197-243's
+    pattern -- workers render 1-spp tiles, merge_tile folds each into the image, to_image_rgb_u8
+    displays it -- without the tile buffer leaving the device.  The film's merges are serialised; every
+    call reports its place in that order (merge_index), and a snapshot says how many it contains."""
+
+    def __init__(self, width, height, device=0):
+        self.width, self.height, self.device = width, height, device
+        self.merges_seen = 0  # of the last snapshot taken through this object
+        self.handle = None
+        h = C.c_void_p()
+        N.check(N.lib().vr_film_create(width, height, device, C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if self.handle is not None:
+            N.lib().vr_film_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def clear(self):
+        """Back to AccumulationBuffer.new; the merge index restarts at 0."""
+        N.check(N.lib().vr_film_clear(self.handle))
+
+    def partial_render_scene(self, scene, tile: Tile):
+        """partial_render_scene + merge_tile (main.rs:204,214-216): one sample per pixel of `tile`, the
+        sample index from the scene's pass counter.  Returns (merge_index, first_sample)."""
+        ds = _scene_handle(scene, self.device)
+        m = N.FilmMerge()
+        N.check(N.lib().vr_film_partial_render_scene(self.handle, ds.handle, tile._c(), C.byref(m)))
+        return m.merge_index, m.first_sample
+
+    def render_tile(self, scene, tile: Tile, spp, seed, first_sample=0):
+        """spp samples per pixel of `tile` with an explicit seed / sample range into a fresh tile buffer,
+        merged into the film.  Returns (merge_index, first_sample)."""
+        ds = _scene_handle(scene, self.device)
+        p = _params(tile, self.height, self.width, spp, seed, first_sample, False)
+        m = N.FilmMerge()
+        N.check(N.lib().vr_film_render_tile(self.handle, ds.handle, C.byref(p), C.byref(m)))
+        return m.merge_index, m.first_sample
+
+    def merge_state(self, tile: Tile, state_ptr, stream_ptr=None):
+        """merge_tile of device records of `tile` (render_tile_device's layout) produced on the stream;
+        only enqueues.  Returns the merge_index."""
+        m = N.FilmMerge()
+        N.check(N.lib().vr_film_merge_state(self.handle, tile._c(), C.c_void_p(state_ptr),
+                                            C.c_void_p(stream_ptr or 0), C.byref(m)))
+        return m.merge_index
+
+    def read(self):
+        """Snapshot -> (AccumulationBuffer, merges_seen): the buffer holds exactly the successful merges
+        with index < merges_seen."""
+        out = AccumulationBuffer._for_output(self.width, self.height)
+        oc = out._c()
+        seen = C.c_uint64()
+        N.check(N.lib().vr_film_read(self.handle, C.byref(oc), C.byref(seen)))
+        self.merges_seen = seen.value
+        return out, seen.value
+
+    def to_image_rgb_u8(self) -> "ImageRgbU8":
+        """to_image_rgb_u8(&ClampingToneMapper) of a snapshot (3 bytes per pixel cross PCIe);
+        `merges_seen` of this object says which merges it shows."""
+        out = np.empty((self.height, self.width, 3), dtype=np.uint8)
+        seen = C.c_uint64()
+        N.check(N.lib().vr_film_to_image_rgb_u8(self.handle, out.ctypes.data_as(C.c_void_p), C.byref(seen)))
+        self.merges_seen = seen.value
+        return ImageRgbU8(out)
+
+    def to_image_rgb_u8_device(self, rgb_ptr, stream_ptr=None):
+        """The same bytes into device memory (3 per pixel), enqueued on a stream.  Returns merges_seen."""
+        seen = C.c_uint64()
+        N.check(N.lib().vr_film_to_image_rgb_u8_device(self.handle, C.c_void_p(rgb_ptr), C.c_void_p(stream_ptr or 0),
+                                                       C.byref(seen)))
+        self.merges_seen = seen.value
+        return seen.value
 
 
 def tone_map_device(state_ptr, pixel_count, rgb_ptr, stream_ptr=None, device=0):
