@@ -422,6 +422,55 @@ typedef struct vr_hit_record {
 int vr_trace_rays(const vr_scene* scene, uint64_t n, const double* origins, const double* directions,
                   vr_hit_record* out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Ray queries: Sampler::sample(&Ray) -> Option<IntersectionInfo> (sampler.rs:9-20) and its
+ * `.is_some()` form (the Whitted shadow rays, whitted_integrator.rs:37-38) for a batch of caller-
+ * supplied rays, walked over the render kernel's 4-wide tree.  Added under ABI 10 (VR_HAS_RAY_QUERY).
+ *
+ * Directions are unit length, as Ray's fields always are: the distance cull compares the ray
+ *   parameter with Euclidean distances and the f32 box tests' error bound assumes |d| = 1.
+ *   VR_QUERY_NORMALIZE makes them so on the device with the reference's normalize (d * (1 / |d|)).
+ *   Without the flag a direction that is not unit length gives unspecified hits, never an
+ *   out-of-bounds access.  Origins may lie anywhere (the error bound carries |o|).
+ * Results are the reference's Sampler::sample: among objects the earlier one wins distance ties,
+ *   inside a BVH the later in-order leaf; boxes are tested as lines (no t >= 0 clamp); a triangle
+ *   counts only if the exact f64 line test passes on its own leaf box and on its mesh's root box.
+ * Errors: n == 0 returns VR_OK and touches nothing; a null scene, a null array with n > 0 or an
+ *   unknown flag bit: VR_ERROR_INVALID_ARGUMENT; a VR_SCENE_HOST_ONLY scene: VR_ERROR_HOST_ONLY; a
+ *   tree deeper than the largest traversal stack (48): VR_ERROR_UNSUPPORTED.
+ * Outputs are written for indices < n only, every field of them (a miss: zeros).
+ * --------------------------------------------------------------------------------------------- */
+#define VR_HAS_RAY_QUERY 1
+
+typedef struct vr_ray_hit { /* 32 B: the compact answer of Sampler::sample */
+    double distance;        /* IntersectionInfo::distance; 0 when valid == 0 */
+    int64_t primitive;      /* as vr_hit_record::primitive (list position / reference leaf position) */
+    int32_t object;         /* scene object index */
+    int32_t valid;
+    uint64_t reserved;      /* written as 0: pads the record to 32 B, two aligned 16-B stores per ray */
+} vr_ray_hit;
+
+#define VR_QUERY_NORMALIZE 1u      /* apply Ray::new (mod.rs:41-46, d * (1/|d|)) to each direction first */
+/* walk the binary f64 tree (the walk of vr_trace_rays) instead of the 4-wide tree: the same answers
+ * bit for bit; for tests and A/B timing */
+#define VR_QUERY_REFERENCE_WALK 2u
+
+/* Sampler::sample for n rays.  origins / directions: device [n][3] f64; hits: device [n]; records:
+ * NULL, or device [n] vr_hit_record (location, normal, tangent, cotangent, retro as well: the bits
+ * of vr_trace_rays).  Only enqueues on `stream` (NULL = the null stream) of the scene's device; no
+ * host synchronisation. */
+int vr_query_closest_device(const vr_scene* scene, uint64_t n, const double* origins, const double* directions,
+                            uint32_t flags, vr_ray_hit* hits, vr_hit_record* records, void* stream);
+/* Sampler::sample(ray).is_some(): hit[i] = 1 or 0, device [n] bytes.  Only enqueues. */
+int vr_query_any_device(const vr_scene* scene, uint64_t n, const double* origins, const double* directions,
+                        uint32_t flags, uint8_t* hit, void* stream);
+/* Host-array forms: staged through a call context exactly as vr_trace_rays.  Thread-safe,
+ * re-entrant, return when done. */
+int vr_query_closest(const vr_scene* scene, uint64_t n, const double* origins, const double* directions,
+                     uint32_t flags, vr_ray_hit* hits, vr_hit_record* records);
+int vr_query_any(const vr_scene* scene, uint64_t n, const double* origins, const double* directions,
+                 uint32_t flags, uint8_t* hit);
+
 /* Host helpers (scene setup; no device work). */
 /* Spectrum::reflection_from_linear_rgb (spectrum.rs:81-165): 32 samples over [380, 720] nm. */
 int vr_spectrum_reflection_from_linear_rgb(double red, double green, double blue, double out[32]);

@@ -11,7 +11,8 @@ SRC=$(mktemp -d)
 git archive "$REV" vanrijn_amd/csrc include | tar -x -C "$SRC"
 FLAGS=$(python3 vanrijn_amd/build.py --print-flags)
 PIDS=""
-for s in vr_render.hip vr_image.hip vr_build.hip vr_host.cpp; do
+# the revision's own translation units (an older one may have fewer than the working tree)
+for s in $(cd $SRC/vanrijn_amd/csrc && ls *.hip *.cpp); do
   /opt/rocm/bin/hipcc $FLAGS "$@" -c $SRC/vanrijn_amd/csrc/$s -o $SRC/${s%.*}.o 2>/dev/null &
   PIDS="$PIDS $!"
 done

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build several A/B variants of the library in parallel into abx/lib<name>.so (travels to the GPU box; git-ignored): the other three
+# Build several A/B variants of the library in parallel into abx/lib<name>.so (travels to the GPU box; git-ignored): the other
 # translation units are compiled once; each variant recompiles vr_render.hip with its own flags.
 #   bash tools/variant_libs.sh base "" split "-DVR_NODE_SPLIT_LOAD" ...
 set -eu
@@ -8,7 +8,8 @@ cd "$(dirname "$0")/.."
 FLAGS=$(python3 vanrijn_amd/build.py --print-flags)
 COMMON=$(mktemp -d)
 mkdir -p abx
-for s in vr_image.hip vr_build.hip vr_host.cpp; do
+OTHERS=$(python3 vanrijn_amd/build.py --print-sources | tr ' ' '\n' | grep -v '^vr_render.hip$')
+for s in $OTHERS; do
   /opt/rocm/bin/hipcc $FLAGS -c vanrijn_amd/csrc/$s -o $COMMON/${s%.*}.o &
 done
 while [ $# -ge 2 ]; do
@@ -18,8 +19,9 @@ while [ $# -ge 2 ]; do
 done
 wait
 for name in $NAMES; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $COMMON/render_$name.o $COMMON/vr_image.o \
-      $COMMON/vr_build.o $COMMON/vr_host.o -lz -o abx/lib$name.so
+  OBJS=""
+  for s in $OTHERS; do OBJS="$OBJS $COMMON/${s%.*}.o"; done
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $COMMON/render_$name.o $OBJS -lz -o abx/lib$name.so
   echo abx/lib$name.so
 done
 rm -rf "$COMMON"

@@ -5,7 +5,8 @@ include/vanrijn_amd.h).  This package is the host-side mirror of the reference's
 library; every pixel is computed on the GPU.
 """
 from .render import (AccumulationBuffer, Film, ImageRgbU8, Tile, TileIterator, partial_render_scene, render_samples,
-                     render_tile, render_tile_device, resolve_state, tone_map_device, trace_rays)
+                     render_tile, render_tile_device, resolve_state, tone_map_device, trace_rays, RAY_HIT_DTYPE,
+                     query_any, query_any_device, query_closest, query_closest_device)
 from .scene import (BoundingVolumeHierarchy, ColourRgbF, DeviceScene, DirectionalLight, LambertianMaterial, Mesh,
                     NamedColour, PhongMaterial, Plane, WhittedIntegrator, ReflectiveMaterial, Scene, SceneSpec, SmoothTransparentDialectric, Sphere,
                     Spectrum, load_obj)
@@ -16,6 +17,7 @@ __all__ = [
     "render_tile_device", "resolve_state", "tone_map_device", "trace_rays", "BoundingVolumeHierarchy", "ColourRgbF", "DeviceScene",
     "LambertianMaterial", "Mesh", "NamedColour", "PhongMaterial", "Plane", "ReflectiveMaterial", "Scene", "SceneSpec",
     "SmoothTransparentDialectric", "Sphere", "Spectrum", "load_obj", "DirectionalLight", "WhittedIntegrator",
+    "RAY_HIT_DTYPE", "query_any", "query_any_device", "query_closest", "query_closest_device",
 ]
 
 

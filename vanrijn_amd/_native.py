@@ -140,6 +140,14 @@ class HitRecord(C.Structure):
                 ("cotangent", C.c_double * 3), ("retro", C.c_double * 3)]
 
 
+class RayHit(C.Structure):
+    _fields_ = [("distance", C.c_double), ("primitive", C.c_int64), ("object", C.c_int32), ("valid", C.c_int32),
+                ("reserved", C.c_uint64)]
+
+
+QUERY_NORMALIZE, QUERY_REFERENCE_WALK = 1, 2
+
+
 # every function declared in include/vanrijn_amd.h: name -> (restype, argtypes)
 _p, _u32, _u64, _i32, _d = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32, C.c_double
 SIGNATURES = {
@@ -157,6 +165,10 @@ SIGNATURES = {
     "vr_merge_tile": (C.c_int, [C.POINTER(AccumulationBufferC), TileC, C.POINTER(AccumulationBufferC)]),
     "vr_render_samples": (C.c_int, [_p, C.POINTER(RenderParams), _p]),
     "vr_trace_rays": (C.c_int, [_p, _u64, _p, _p, _p]),
+    "vr_query_closest_device": (C.c_int, [_p, _u64, _p, _p, _u32, _p, _p, _p]),
+    "vr_query_any_device": (C.c_int, [_p, _u64, _p, _p, _u32, _p, _p]),
+    "vr_query_closest": (C.c_int, [_p, _u64, _p, _p, _u32, _p, _p]),
+    "vr_query_any": (C.c_int, [_p, _u64, _p, _p, _u32, _p]),
     "vr_spectrum_reflection_from_linear_rgb": (C.c_int, [_d, _d, _d, _p]),
     "vr_spectrum_intensity_at_wavelength": (_d, [C.POINTER(Spectrum), _d]),
     "vr_colour_xyz_for_wavelength": (None, [_d, _p]),

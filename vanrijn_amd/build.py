@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libvanrijn_amd.so")
-SOURCES = ["vr_render.hip", "vr_image.hip", "vr_build.hip", "vr_host.cpp"]
+SOURCES = ["vr_render.hip", "vr_query.hip", "vr_image.hip", "vr_build.hip", "vr_host.cpp"]
 HEADERS = ["vr_layout.h", "vr_device.h", "rgb_spectrum_tables.h", "vr_exp_table.h", os.path.join("..", "..", "include", "vanrijn_amd.h")]
 
 FLAGS = [
@@ -85,6 +85,9 @@ def build(force=False, verbose=False):
 if __name__ == "__main__":
     if "--print-flags" in sys.argv:  # the compile flags on one line, for the A/B scripts; builds nothing
         print(" ".join(compile_flags_of()))
+        sys.exit(0)
+    if "--print-sources" in sys.argv:  # the translation units, for the same scripts
+        print(" ".join(SOURCES))
         sys.exit(0)
     build(force="--force" in sys.argv, verbose=True)
     print(LIB)

@@ -2256,6 +2256,109 @@ int vr_trace_rays(const vr_scene* s, uint64_t n, const double* origins, const do
     return VR_OK;
 }
 
+// ---- ray queries (vr_query.hip) ----
+namespace {
+
+// the checks every query entry point makes before its first device call; *go: there is work to do
+int query_check(const vr_scene* s, uint64_t n, const void* origins, const void* directions, uint32_t flags,
+                const void* out, bool* go) {
+    *go = false;
+    if (!s) return fail(VR_ERROR_INVALID_ARGUMENT, "null scene");
+    if (flags & ~(VR_QUERY_NORMALIZE | VR_QUERY_REFERENCE_WALK))
+        return fail(VR_ERROR_INVALID_ARGUMENT, "unknown query flag");
+    if (n == 0) return VR_OK;
+    if (!origins || !directions || !out) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
+    if (s->host_only) return fail(VR_ERROR_HOST_ONLY, "scene was created with VR_SCENE_HOST_ONLY");
+    if (n > UINT64_MAX / sizeof(vr_hit_record)) return fail(VR_ERROR_INVALID_ARGUMENT, "ray count overflows");
+    const int depth = (flags & VR_QUERY_REFERENCE_WALK) ? stack_depth(s) : wide_stack_depth(s);
+    if (depth > 48) return fail(VR_ERROR_UNSUPPORTED, "BVH deeper than the largest traversal stack (48)");
+    *go = true;
+    return VR_OK;
+}
+
+// enqueue one query launch on `st` (device pointers)
+int query_enqueue(const vr_scene* s, uint64_t n, const double* origins, const double* directions, uint32_t flags,
+                  bool any, void* hits, void* records, hipStream_t st) {
+    vr::QueryArgs a{};
+    a.scene = s->dev;
+    a.n = n;
+    a.origins = origins;
+    a.directions = directions;
+    a.hits = hits;
+    a.records = records;
+    a.flags = flags;
+    a.any = any ? 1u : 0u;
+    const int depth = (flags & VR_QUERY_REFERENCE_WALK) ? stack_depth(s) : wide_stack_depth(s);
+    // enough workgroups for every CU's LDS several times over; larger batches take the grid stride
+    const int lr = vr::launch_query(a, depth, std::max(1, s->cu_count) * 32, st);
+    if (lr) return fail(lr == -1000 ? VR_ERROR_UNSUPPORTED : VR_ERROR_DEVICE, vr::device_error_string(lr));
+    return VR_OK;
+}
+
+// the host-array forms: inputs and outputs staged through a call context, as vr_trace_rays
+int query_host(const vr_scene* s, uint64_t n, const double* origins, const double* directions, uint32_t flags,
+               bool any, void* hits, vr_hit_record* records) {
+    bool go;
+    int rc = query_check(s, n, origins, directions, flags, hits, &go);
+    if (rc || !go) return rc;
+    VR_HIP(hipSetDevice(s->device));
+    vr_scene* ms = const_cast<vr_scene*>(s);
+    CtxLease L(ms);
+    rc = ctx_acquire(ms, &L.c);
+    if (rc) return rc;
+    CallCtx* c = L.c;
+    const hipStream_t st = c->stream;
+    VR_HIP(hipStreamWaitEvent(st, c->done, 0));
+    DoneOnExit guard{c->done, st};
+    const size_t in_bytes = n * 3 * sizeof(double);
+    const size_t hit_bytes = any ? (size_t)((n + 15) & ~(uint64_t)15) : n * sizeof(vr_ray_hit);
+    const size_t rec_bytes = records ? n * sizeof(vr_hit_record) : 0;
+    rc = ctx_grow(&c->scratch, &c->scratch_bytes, 2 * in_bytes + hit_bytes + rec_bytes, c->done);
+    if (rc) return rc;
+    char* b = (char*)c->scratch;
+    VR_HIP(hipMemcpyAsync(b, origins, in_bytes, hipMemcpyHostToDevice, st));
+    VR_HIP(hipMemcpyAsync(b + in_bytes, directions, in_bytes, hipMemcpyHostToDevice, st));
+    char* d_hits = b + 2 * in_bytes;
+    char* d_rec = records ? d_hits + hit_bytes : nullptr;
+    rc = query_enqueue(s, n, (const double*)b, (const double*)(b + in_bytes), flags, any, d_hits, d_rec, st);
+    if (rc) return rc;
+    VR_HIP(hipMemcpyAsync(hits, d_hits, any ? (size_t)n : hit_bytes, hipMemcpyDeviceToHost, st));
+    if (records) VR_HIP(hipMemcpyAsync(records, d_rec, rec_bytes, hipMemcpyDeviceToHost, st));
+    VR_HIP(hipEventRecord(c->done, st));
+    VR_HIP(hipStreamSynchronize(st));
+    return VR_OK;
+}
+
+}  // namespace
+
+int vr_query_closest_device(const vr_scene* s, uint64_t n, const double* origins, const double* directions,
+                            uint32_t flags, vr_ray_hit* hits, vr_hit_record* records, void* stream) {
+    bool go;
+    const int rc = query_check(s, n, origins, directions, flags, hits, &go);
+    if (rc || !go) return rc;
+    VR_HIP(hipSetDevice(s->device));
+    return query_enqueue(s, n, origins, directions, flags, false, hits, records, (hipStream_t)stream);
+}
+
+int vr_query_any_device(const vr_scene* s, uint64_t n, const double* origins, const double* directions,
+                        uint32_t flags, uint8_t* hit, void* stream) {
+    bool go;
+    const int rc = query_check(s, n, origins, directions, flags, hit, &go);
+    if (rc || !go) return rc;
+    VR_HIP(hipSetDevice(s->device));
+    return query_enqueue(s, n, origins, directions, flags, true, hit, nullptr, (hipStream_t)stream);
+}
+
+int vr_query_closest(const vr_scene* s, uint64_t n, const double* origins, const double* directions, uint32_t flags,
+                     vr_ray_hit* hits, vr_hit_record* records) {
+    return query_host(s, n, origins, directions, flags, false, hits, records);
+}
+
+int vr_query_any(const vr_scene* s, uint64_t n, const double* origins, const double* directions, uint32_t flags,
+                 uint8_t* hit) {
+    return query_host(s, n, origins, directions, flags, true, hit, nullptr);
+}
+
 int vr_merge_tile(vr_accumulation_buffer* dst, vr_tile t, const vr_accumulation_buffer* src) {
     if (!dst || !src || !dst->colour || !dst->weight || !src->colour || !src->weight)
         return fail(VR_ERROR_INVALID_ARGUMENT, "null buffer");

@@ -216,6 +216,18 @@ struct TraceArgs {
     void* out;  // vr_hit_record*
 };
 
+// vr_query.hip: a batch of caller-supplied rays (device pointers)
+struct QueryArgs {
+    DeviceScene scene;
+    uint64_t n;
+    const double* origins;     // [n][3]
+    const double* directions;  // [n][3]
+    void* hits;                // closest: vr_ray_hit[n]; any: uint8_t[n]
+    void* records;             // closest: vr_hit_record[n] or nullptr
+    uint32_t flags;            // VR_QUERY_*
+    uint32_t any;              // 1: Sampler::sample(ray).is_some()
+};
+
 // counters[] slots of the counting kernel variant
 enum Counter : int {
     kCntBoxTests = 0,
@@ -285,6 +297,10 @@ int device_build_sah(TriVerts* tris, TriNormals* normals, uint32_t n, int32_t no
 // vr_build.hip: Node4 / Node4x records from a device-built binary tree and a host-made descriptor
 int device_fill_wide(const Node* bin, const int32_t* desc, uint64_t n4, Node4* out4, void* stream);
 int launch_trace(const TraceArgs& args, int stack_depth, void* stream);
+// vr_query.hip: closest / any hit for args.n rays; stack_depth: the LDS stack entries the walked tree
+// needs (the 4-wide tree's, or the binary tree's with VR_QUERY_REFERENCE_WALK); at most grid_limit
+// workgroups (grid-stride beyond).  Only enqueues.  -1000: deeper than the largest stack class
+int launch_query(const QueryArgs& args, int stack_depth, int grid_limit, void* stream);
 #ifdef VR_SPLIT_PROBE  // analysis builds (vr_render.hip)
 int launch_trace_probe(const RenderArgs& args, int stack_depth, int minw, bool s16, int grid, void* stream);
 #endif

@@ -25,6 +25,9 @@ SAMPLE_RECORD_DTYPE = np.dtype([("wavelength", "<f8"), ("intensity", "<f8"), ("x
 HIT_RECORD_DTYPE = np.dtype([("valid", "<i4"), ("object", "<i4"), ("primitive", "<i8"), ("distance", "<f8"),
                              ("location", "<f8", (3,)), ("normal", "<f8", (3,)), ("tangent", "<f8", (3,)),
                              ("cotangent", "<f8", (3,)), ("retro", "<f8", (3,))])
+RAY_HIT_DTYPE = np.dtype([("distance", "<f8"), ("primitive", "<i8"), ("object", "<i4"), ("valid", "<i4"),
+                          ("reserved", "<u8")])
+assert RAY_HIT_DTYPE.itemsize == C.sizeof(N.RayHit) == 32
 assert SAMPLE_RECORD_DTYPE.itemsize == C.sizeof(N.SampleRecord)
 assert HIT_RECORD_DTYPE.itemsize == C.sizeof(N.HitRecord)
 
@@ -244,6 +247,62 @@ def trace_rays(scene, origins, directions, device=0):
     N.check(N.lib().vr_trace_rays(ds.handle, len(o), o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p),
                                   out.ctypes.data_as(C.c_void_p)))
     return out
+
+
+def _query_flags(normalize, reference_walk):
+    return (N.QUERY_NORMALIZE if normalize else 0) | (N.QUERY_REFERENCE_WALK if reference_walk else 0)
+
+
+def _rays(origins, directions):
+    o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
+    if len(o) != len(d):
+        raise ValueError("origins and directions differ in length")
+    return o, d
+
+
+def query_closest(scene, origins, directions, normalize=False, records=False, reference_walk=False, device=0):
+    """Sampler::sample for a batch of host rays over the 4-wide tree (vr_query_closest): the hits as
+    a RAY_HIT_DTYPE array, or (hits, HIT_RECORD_DTYPE records) with `records`.  Directions are unit
+    length unless `normalize` (Ray::new on the device); `reference_walk`: the binary f64 tree, the
+    same answers bit for bit."""
+    ds = _scene_handle(scene, device)
+    o, d = _rays(origins, directions)
+    hits = np.zeros(len(o), dtype=RAY_HIT_DTYPE)
+    rec = np.zeros(len(o), dtype=HIT_RECORD_DTYPE) if records else None
+    N.check(N.lib().vr_query_closest(ds.handle, len(o), o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p),
+                                     _query_flags(normalize, reference_walk), hits.ctypes.data_as(C.c_void_p),
+                                     rec.ctypes.data_as(C.c_void_p) if records else None))
+    return (hits, rec) if records else hits
+
+
+def query_any(scene, origins, directions, normalize=False, reference_walk=False, device=0):
+    """Sampler::sample(ray).is_some() for a batch of host rays (vr_query_any): a bool array."""
+    ds = _scene_handle(scene, device)
+    o, d = _rays(origins, directions)
+    hit = np.zeros(len(o), dtype=np.uint8)
+    N.check(N.lib().vr_query_any(ds.handle, len(o), o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p),
+                                 _query_flags(normalize, reference_walk), hit.ctypes.data_as(C.c_void_p)))
+    return hit.astype(bool)
+
+
+def query_closest_device(scene, n, origins_ptr, directions_ptr, hits_ptr, records_ptr=None, stream_ptr=None,
+                         normalize=False, reference_walk=False, device=0):
+    """Enqueue Sampler::sample for n rays in device memory ([n][3] f64 each) into device vr_ray_hit
+    records at `hits_ptr` (and vr_hit_record at `records_ptr`) on a stream; no synchronisation."""
+    ds = _scene_handle(scene, device)
+    N.check(N.lib().vr_query_closest_device(ds.handle, n, C.c_void_p(origins_ptr), C.c_void_p(directions_ptr),
+                                            _query_flags(normalize, reference_walk), C.c_void_p(hits_ptr),
+                                            C.c_void_p(records_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+
+def query_any_device(scene, n, origins_ptr, directions_ptr, hit_ptr, stream_ptr=None, normalize=False,
+                     reference_walk=False, device=0):
+    """Enqueue the any-hit query for n device rays into n device bytes (1 / 0) on a stream."""
+    ds = _scene_handle(scene, device)
+    N.check(N.lib().vr_query_any_device(ds.handle, n, C.c_void_p(origins_ptr), C.c_void_p(directions_ptr),
+                                        _query_flags(normalize, reference_walk), C.c_void_p(hit_ptr),
+                                        C.c_void_p(stream_ptr or 0)))
 
 
 def render_tile_device(scene, tile: Tile, height, width, spp, seed, first_sample, state_ptr, stream_ptr=None,
