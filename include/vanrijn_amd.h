@@ -471,6 +471,85 @@ int vr_query_closest(const vr_scene* scene, uint64_t n, const double* origins, c
 int vr_query_any(const vr_scene* scene, uint64_t n, const double* origins, const double* directions,
                  uint32_t flags, uint8_t* hit);
 
+/* ---------------------------------------------------------------------------------------------
+ * The integrators for caller-supplied rays: the body of partial_render_scene's loop (camera.rs:107-
+ * 120: sampler.sample(&ray), then integrator.integrate(..) or the zero photon) for a batch of rays
+ * that come from the caller instead of the scene's ImageSampler -- another camera, light probes,
+ * bounce rays of the caller's own.  Added under ABI 10 (VR_HAS_INTEGRATE).
+ *
+ * Per ray i: the closest hit is found with the rules of vr_query_closest (unit directions;
+ *   VR_QUERY_NORMALIZE applies Ray::new's normalisation on the device).  A miss gives the photon
+ *   {0, 0} with flags 0 and bounces 0 (camera.rs:110-113; the sky is not sampled for a primary miss,
+ *   as in the reference).  A hit sets flags bit 0; the wavelength is Photon::random_wavelength
+ *   (380 + 360 x Standard), the call's first draw of the ray's stream, when `wavelengths` is NULL,
+ *   else wavelengths[i] and no draw is spent.  Then the scene's integrator runs exactly as in the
+ *   render: SimpleRandomIntegrator, or Whitted where the scene selects it, all four material kinds,
+ *   VR_RECURSION_LIMIT.  `intensity` is the photon's intensity before the x360 pdf scale
+ *   (vr_sample_record::intensity, what vr_accumulate_photons_device reads); wavelength, bounces and
+ *   flags are vr_sample_record's bit for bit: wavelength 0 with flags bit 1 after the recursion limit,
+ *   flags bit 2 and photon {0, 0} for a singular shading basis.  No path stops early.
+ * Random stream ("vr-hash32 v2"): ray i draws from the stream whose
+ *   (pixel << 32) + sample is stream_ids[i], or ((first_stream + i) << 32) + sample when stream_ids is
+ *   NULL, under `seed`; the stream's first `first_draw` draws are skipped.  first_draw = 2 with drawn
+ *   wavelengths (3 with given ones) replays the material draws of pixel row * width + col of a render
+ *   with that seed, whose draws 0 and 1 are the camera jitter.  first_stream + n > 2^32 or
+ *   sample >= 2^32: VR_ERROR_UNSUPPORTED.
+ * Errors: n == 0 returns VR_OK and touches nothing; a null scene or params, a null origins /
+ *   directions / photons with n > 0 or a flag bit other than VR_QUERY_NORMALIZE:
+ *   VR_ERROR_INVALID_ARGUMENT; a VR_SCENE_HOST_ONLY scene: VR_ERROR_HOST_ONLY; a tree deeper than the
+ *   largest traversal stack (48): VR_ERROR_UNSUPPORTED -- all before the first device call.
+ *   VR_ERROR_SINGULAR_BASIS: returned by the host form; the device form records it in the stream's
+ *   sticky error word, read by vr_stream_check_error(scene, stream), as vr_render_tile_device does.
+ *   vr_debug_set_fault_object is honoured.
+ * Outputs are written for indices < n only.  photons must be 16-byte aligned, info 8-byte aligned
+ *   (any hipMalloc or torch allocation is).
+ * --------------------------------------------------------------------------------------------- */
+#define VR_HAS_INTEGRATE 1
+
+typedef struct vr_photon { /* 16 B: Photon (photon.rs) */
+    double wavelength;
+    double intensity;
+} vr_photon;
+
+typedef struct vr_path_info { /* 8 B */
+    int32_t bounces; /* as vr_sample_record::bounces */
+    int32_t flags;   /* as vr_sample_record::flags */
+} vr_path_info;
+
+typedef struct vr_integrate_params {
+    uint64_t seed;         /* as vr_render_params::seed */
+    uint64_t first_stream; /* stream_ids == NULL: ray i draws from stream (seed, first_stream + i, sample) */
+    uint64_t sample;
+    uint32_t first_draw;   /* draws of the stream skipped before the first one this call takes */
+    uint32_t flags;        /* VR_QUERY_NORMALIZE only */
+} vr_integrate_params;
+
+/* origins / directions: device [n][3] f64; wavelengths: NULL or device [n] f64; stream_ids: NULL or
+ * device [n] u64; photons: device [n]; info: NULL or device [n].  Only enqueues on `stream` (NULL = the
+ * null stream) of the scene's device; no host synchronisation. */
+int vr_integrate_rays_device(const vr_scene* scene, uint64_t n, const double* origins, const double* directions,
+                             const double* wavelengths, const uint64_t* stream_ids,
+                             const vr_integrate_params* params, vr_photon* photons, vr_path_info* info, void* stream);
+/* Host-array form: staged through a call context as vr_query_closest.  Thread-safe, re-entrant,
+ * returns when done. */
+int vr_integrate_rays(const vr_scene* scene, uint64_t n, const double* origins, const double* directions,
+                      const double* wavelengths, const uint64_t* stream_ids, const vr_integrate_params* params,
+                      vr_photon* photons, vr_path_info* info);
+/* update_pixel (accumulation_buffer.rs:44-60, weight 1) of photons[s * pixel_count + p], s = 0 ..
+ * spp - 1 in order, into pixel p's record at `state` (the layout of vr_render_tile_device; accumulate
+ * 0: from a fresh record, 1: continuing the records there): the render's ordered reduce on its own.
+ * Device pointers on `device`, 16-byte aligned; only enqueues on `stream`. */
+int vr_accumulate_photons_device(double* state, const vr_photon* photons, uint64_t pixel_count, uint32_t spp,
+                                 uint32_t accumulate, int32_t device, void* stream);
+/* ImageSampler::ray_for_pixel (camera.rs:24-66) of the scene's camera for every (sample, pixel) of
+ * params->tile: entry s * (tile pixels) + p (p row-major in the tile) holds sample
+ * params->first_sample + s of pixel p -- its origin, its direction (normalised once, as Ray::new) and
+ * its stream id ((row * width + col) << 32) + sample; the jitter is draws 0 and 1 of that stream, x
+ * before y.  Device arrays of spp * (tile pixels) entries; only enqueues on `stream`.  The way to feed
+ * the scene's own camera through vr_integrate_rays_device, and the model for a caller's camera. */
+int vr_camera_rays_device(const vr_scene* scene, const vr_render_params* params, double* origins,
+                          double* directions, uint64_t* stream_ids, void* stream);
+
 /* Host helpers (scene setup; no device work). */
 /* Spectrum::reflection_from_linear_rgb (spectrum.rs:81-165): 32 samples over [380, 720] nm. */
 int vr_spectrum_reflection_from_linear_rgb(double red, double green, double blue, double out[32]);

@@ -1,5 +1,5 @@
 """VGPR / SGPR / scratch / LDS of the render-kernel instantiations (analysis aid), or of the
-ray-query kernel's when given vr_query.hip.
+ray-query / integrate kernels' when given vr_query.hip / vr_integrate.hip.
     python tools/kernel_resources.py [other/vr_render.hip | vanrijn_amd/csrc/vr_query.hip] [extra hipcc flags]"""
 import os
 import re
@@ -24,10 +24,11 @@ def main():
     meta = open(out).read().split("amdhsa.kernels:")[1]
     for blk in re.split(r"\n  - ", meta):
         name = re.search(r"\.name:\s+(\S+)", blk)
-        args = name and re.search(r"(?:render|query)_kernelIL(.*?)EEEv", name.group(1))
+        args = name and re.search(r"(?:render|query|integrate)_kernelIL(.*?)EEEv", name.group(1))
         if not args:
             continue
-        args = ("query " if "query_kernel" in name.group(1) else "") + args.group(1)
+        args = ("query " if "query_kernel" in name.group(1) else
+                "integrate " if "integrate_kernel" in name.group(1) else "") + args.group(1)
         f = {k: re.search(r"\." + k + r":\s+(\d+)", blk) for k in
              ("vgpr_count", "sgpr_count", "sgpr_spill_count", "vgpr_spill_count", "private_segment_fixed_size",
               "group_segment_fixed_size")}

@@ -6,7 +6,9 @@ library; every pixel is computed on the GPU.
 """
 from .render import (AccumulationBuffer, Film, ImageRgbU8, Tile, TileIterator, partial_render_scene, render_samples,
                      render_tile, render_tile_device, resolve_state, tone_map_device, trace_rays, RAY_HIT_DTYPE,
-                     query_any, query_any_device, query_closest, query_closest_device)
+                     query_any, query_any_device, query_closest, query_closest_device, PHOTON_DTYPE,
+                     PATH_INFO_DTYPE, integrate_rays, integrate_rays_device, accumulate_photons_device,
+                     camera_rays_device)
 from .scene import (BoundingVolumeHierarchy, ColourRgbF, DeviceScene, DirectionalLight, LambertianMaterial, Mesh,
                     NamedColour, PhongMaterial, Plane, WhittedIntegrator, ReflectiveMaterial, Scene, SceneSpec, SmoothTransparentDialectric, Sphere,
                     Spectrum, load_obj)
@@ -18,6 +20,8 @@ __all__ = [
     "LambertianMaterial", "Mesh", "NamedColour", "PhongMaterial", "Plane", "ReflectiveMaterial", "Scene", "SceneSpec",
     "SmoothTransparentDialectric", "Sphere", "Spectrum", "load_obj", "DirectionalLight", "WhittedIntegrator",
     "RAY_HIT_DTYPE", "query_any", "query_any_device", "query_closest", "query_closest_device",
+    "PHOTON_DTYPE", "PATH_INFO_DTYPE", "integrate_rays", "integrate_rays_device", "accumulate_photons_device",
+    "camera_rays_device",
 ]
 
 

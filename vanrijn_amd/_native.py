@@ -148,6 +148,19 @@ class RayHit(C.Structure):
 QUERY_NORMALIZE, QUERY_REFERENCE_WALK = 1, 2
 
 
+class Photon(C.Structure):
+    _fields_ = [("wavelength", C.c_double), ("intensity", C.c_double)]
+
+
+class PathInfo(C.Structure):
+    _fields_ = [("bounces", C.c_int32), ("flags", C.c_int32)]
+
+
+class IntegrateParams(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("first_stream", C.c_uint64), ("sample", C.c_uint64),
+                ("first_draw", C.c_uint32), ("flags", C.c_uint32)]
+
+
 # every function declared in include/vanrijn_amd.h: name -> (restype, argtypes)
 _p, _u32, _u64, _i32, _d = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32, C.c_double
 SIGNATURES = {
@@ -169,6 +182,10 @@ SIGNATURES = {
     "vr_query_any_device": (C.c_int, [_p, _u64, _p, _p, _u32, _p, _p]),
     "vr_query_closest": (C.c_int, [_p, _u64, _p, _p, _u32, _p, _p]),
     "vr_query_any": (C.c_int, [_p, _u64, _p, _p, _u32, _p]),
+    "vr_integrate_rays_device": (C.c_int, [_p, _u64, _p, _p, _p, _p, C.POINTER(IntegrateParams), _p, _p, _p]),
+    "vr_integrate_rays": (C.c_int, [_p, _u64, _p, _p, _p, _p, C.POINTER(IntegrateParams), _p, _p]),
+    "vr_accumulate_photons_device": (C.c_int, [_p, _p, _u64, _u32, _u32, _i32, _p]),
+    "vr_camera_rays_device": (C.c_int, [_p, C.POINTER(RenderParams), _p, _p, _p, _p]),
     "vr_spectrum_reflection_from_linear_rgb": (C.c_int, [_d, _d, _d, _p]),
     "vr_spectrum_intensity_at_wavelength": (_d, [C.POINTER(Spectrum), _d]),
     "vr_colour_xyz_for_wavelength": (None, [_d, _p]),

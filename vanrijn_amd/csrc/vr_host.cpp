@@ -2359,6 +2359,162 @@ int vr_query_any(const vr_scene* s, uint64_t n, const double* origins, const dou
     return query_host(s, n, origins, directions, flags, true, hit, nullptr);
 }
 
+// ---- the integrators for caller-supplied rays (vr_integrate.hip) ----
+namespace {
+
+// the checks both integrate entry points make before their first device call; *go: there is work to do
+int integrate_check(const vr_scene* s, uint64_t n, const void* origins, const void* directions,
+                    const vr_integrate_params* p, const void* photons, bool* go) {
+    *go = false;
+    if (!s || !p) return fail(VR_ERROR_INVALID_ARGUMENT, "null scene or params");
+    if (p->flags & ~VR_QUERY_NORMALIZE) return fail(VR_ERROR_INVALID_ARGUMENT, "unknown integrate flag");
+    if (n == 0) return VR_OK;
+    if (!origins || !directions || !photons) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
+    // the stream's index space, as check_render_params: (pixel << 32) + sample must not carry.  Compared
+    // without forming first_stream + n (it may wrap)
+    const uint64_t lim = 1ull << 32;
+    if (n > lim || p->first_stream > lim - n)
+        return fail(VR_ERROR_UNSUPPORTED, "stream indices past 2^32 (random stream index space)");
+    if (p->sample >= lim) return fail(VR_ERROR_UNSUPPORTED, "sample index past 2^32 (random stream index space)");
+    if (s->host_only) return fail(VR_ERROR_HOST_ONLY, "scene was created with VR_SCENE_HOST_ONLY");
+    if (wide_stack_depth(s) > 48) return fail(VR_ERROR_UNSUPPORTED, "BVH deeper than the largest traversal stack (48)");
+    *go = true;
+    return VR_OK;
+}
+
+uint64_t seed_key_of(uint64_t seed) {  // vr-hash32 v2, as make_args
+    uint64_t z = seed ^ 0x76616E52696A6E31ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// enqueue one integrate launch on `st` (device pointers); err: the error word a singular basis sets
+int integrate_enqueue(const vr_scene* s, uint64_t n, const double* origins, const double* directions,
+                      const double* wavelengths, const uint64_t* stream_ids, const vr_integrate_params* p,
+                      vr_photon* photons, vr_path_info* info, int32_t* err, hipStream_t st) {
+    vr::IntegrateArgs a{};
+    a.scene = s->dev;
+    a.n = n;
+    a.origins = origins;
+    a.directions = directions;
+    a.wavelengths = wavelengths;
+    a.stream_ids = stream_ids;
+    a.seed_key = seed_key_of(p->seed);
+    a.first_stream = p->first_stream;
+    a.sample = p->sample;
+    a.first_draw = p->first_draw;
+    a.flags = p->flags;
+    a.fault_object = s->fault_object;
+    a.error_flag = err;
+    a.photons = photons;
+    a.info = info;
+    const char* g = tuning_env("VR_INTEGRATE_GRID");  // tuning hook: workgroups per CU
+    const int per_cu = g ? std::max(1, atoi(g)) : 32;
+    const int lr = vr::launch_integrate(a, wide_stack_depth(s), std::max(1, s->cu_count) * per_cu, st);
+    if (lr) return fail(lr == -1000 ? VR_ERROR_UNSUPPORTED : VR_ERROR_DEVICE, vr::device_error_string(lr));
+    return VR_OK;
+}
+
+}  // namespace
+
+int vr_integrate_rays_device(const vr_scene* s, uint64_t n, const double* origins, const double* directions,
+                             const double* wavelengths, const uint64_t* stream_ids, const vr_integrate_params* p,
+                             vr_photon* photons, vr_path_info* info, void* stream) {
+    bool go;
+    int rc = integrate_check(s, n, origins, directions, p, photons, &go);
+    if (rc || !go) return rc;
+    VR_HIP(hipSetDevice(s->device));
+    int32_t* slot = nullptr;
+    rc = stream_slot(const_cast<vr_scene*>(s), stream, &slot);
+    if (rc) return rc;
+    return integrate_enqueue(s, n, origins, directions, wavelengths, stream_ids, p, photons, info, slot,
+                             (hipStream_t)stream);
+}
+
+int vr_integrate_rays(const vr_scene* s, uint64_t n, const double* origins, const double* directions,
+                      const double* wavelengths, const uint64_t* stream_ids, const vr_integrate_params* p,
+                      vr_photon* photons, vr_path_info* info) {
+    bool go;
+    int rc = integrate_check(s, n, origins, directions, p, photons, &go);
+    if (rc || !go) return rc;
+    VR_HIP(hipSetDevice(s->device));
+    vr_scene* ms = const_cast<vr_scene*>(s);
+    CtxLease L(ms);
+    rc = ctx_acquire(ms, &L.c);
+    if (rc) return rc;
+    CallCtx* c = L.c;
+    const hipStream_t st = c->stream;
+    VR_HIP(hipStreamWaitEvent(st, c->done, 0));
+    DoneOnExit guard{c->done, st};
+    // [origins | directions | photons | wavelengths | stream ids | info]: every part 16-B aligned
+    const size_t in_bytes = n * 3 * sizeof(double), ph_bytes = n * sizeof(vr_photon);
+    const size_t w8 = (size_t)((n * 8 + 15) & ~(uint64_t)15);
+    const size_t wl_bytes = wavelengths ? w8 : 0, id_bytes = stream_ids ? w8 : 0, info_bytes = info ? w8 : 0;
+    rc = ctx_grow(&c->scratch, &c->scratch_bytes, 2 * ((in_bytes + 15) & ~(size_t)15) + ph_bytes + wl_bytes + id_bytes +
+                                                      info_bytes, c->done);
+    if (rc) return rc;
+    char* const d_o = (char*)c->scratch;
+    char* const d_d = d_o + ((in_bytes + 15) & ~(size_t)15);
+    char* const d_ph = d_d + ((in_bytes + 15) & ~(size_t)15);
+    char* const d_wl = d_ph + ph_bytes;
+    char* const d_id = d_wl + wl_bytes;
+    char* const d_info = d_id + id_bytes;
+    VR_HIP(hipMemcpyAsync(d_o, origins, in_bytes, hipMemcpyHostToDevice, st));
+    VR_HIP(hipMemcpyAsync(d_d, directions, in_bytes, hipMemcpyHostToDevice, st));
+    if (wavelengths) VR_HIP(hipMemcpyAsync(d_wl, wavelengths, n * 8, hipMemcpyHostToDevice, st));
+    if (stream_ids) VR_HIP(hipMemcpyAsync(d_id, stream_ids, n * 8, hipMemcpyHostToDevice, st));
+    rc = integrate_enqueue(s, n, (const double*)d_o, (const double*)d_d, wavelengths ? (const double*)d_wl : nullptr,
+                           stream_ids ? (const uint64_t*)d_id : nullptr, p, (vr_photon*)d_ph,
+                           info ? (vr_path_info*)d_info : nullptr, c->error, st);
+    if (rc) return rc;
+    VR_HIP(hipMemcpyAsync(photons, d_ph, ph_bytes, hipMemcpyDeviceToHost, st));
+    if (info) VR_HIP(hipMemcpyAsync(info, d_info, n * 8, hipMemcpyDeviceToHost, st));
+    VR_HIP(hipEventRecord(c->done, st));
+    return read_and_clear_error(c->error, st);
+}
+
+int vr_accumulate_photons_device(double* state, const vr_photon* photons, uint64_t pixel_count, uint32_t spp,
+                                 uint32_t accumulate, int32_t device, void* stream) {
+    if (pixel_count == 0) return VR_OK;
+    if (!state || !photons) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
+    if (pixel_count > (1ull << 32)) return fail(VR_ERROR_UNSUPPORTED, "more than 2^32 pixels in one call");
+    VR_HIP(hipSetDevice(device));
+    const int lr = vr::launch_accumulate(state, (const double*)photons, pixel_count, spp, accumulate, stream);
+    if (lr) return fail(VR_ERROR_DEVICE, vr::device_error_string(lr));
+    return VR_OK;
+}
+
+int vr_camera_rays_device(const vr_scene* s, const vr_render_params* p, double* origins, double* directions,
+                          uint64_t* stream_ids, void* stream) {
+    int rc = check_render_params(s, p);
+    if (rc) return rc;
+    const uint64_t tw = p->tile.end_column - p->tile.start_column, th = p->tile.end_row - p->tile.start_row;
+    if (tw * th == 0 || p->spp == 0) return VR_OK;
+    if (!origins || !directions || !stream_ids) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
+    if (tw * th > (1ull << 38) / p->spp) return fail(VR_ERROR_UNSUPPORTED, "too many rays in one call (2^38)");
+    VR_HIP(hipSetDevice(s->device));
+    const vr::RenderArgs r = make_args(s, p, nullptr);
+    vr::CameraRaysArgs a{};
+    for (int k = 0; k < 3; ++k) a.camera[k] = s->dev.camera[k];
+    a.start_column = r.start_column;
+    a.start_row = r.start_row;
+    a.tile_width = r.tile_width;
+    a.tile_height = r.tile_height;
+    a.width = r.width;
+    a.height = r.height;
+    a.seed_key = r.seed_key;
+    a.first_sample = r.first_sample;
+    a.spp = r.spp;
+    for (int k = 0; k < 4; ++k) a.film[k] = r.film[k];
+    a.origins = origins;
+    a.directions = directions;
+    a.stream_ids = stream_ids;
+    const int lr = vr::launch_camera_rays(a, stream);
+    if (lr) return fail(VR_ERROR_DEVICE, vr::device_error_string(lr));
+    return VR_OK;
+}
+
 int vr_merge_tile(vr_accumulation_buffer* dst, vr_tile t, const vr_accumulation_buffer* src) {
     if (!dst || !src || !dst->colour || !dst->weight || !src->colour || !src->weight)
         return fail(VR_ERROR_INVALID_ARGUMENT, "null buffer");

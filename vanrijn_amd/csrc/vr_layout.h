@@ -228,6 +228,38 @@ struct QueryArgs {
     uint32_t any;              // 1: Sampler::sample(ray).is_some()
 };
 
+// vr_integrate.hip: the scene's integrator for a batch of caller-supplied rays (device pointers)
+struct IntegrateArgs {
+    DeviceScene scene;
+    uint64_t n;
+    const double* origins;       // [n][3]
+    const double* directions;    // [n][3]
+    const double* wavelengths;   // [n], or nullptr: Photon::random_wavelength from the ray's stream
+    const uint64_t* stream_ids;  // [n] (pixel << 32) + sample, or nullptr: ((first_stream + i) << 32) + sample
+    uint64_t seed_key;           // mix64(seed ^ salt), as RenderArgs::seed_key
+    uint64_t first_stream, sample;
+    uint32_t first_draw;         // draws of the stream skipped before the call's first one
+    uint32_t flags;              // VR_QUERY_NORMALIZE
+    int32_t fault_object;        // as RenderArgs::fault_object
+    int32_t pad;
+    int32_t* error_flag;         // the error word a singular shading basis sets
+    void* photons;               // vr_photon[n]
+    void* info;                  // vr_path_info[n] or nullptr
+};
+
+// vr_integrate.hip: ImageSampler::ray_for_pixel for every (sample, pixel) of a tile, [s][p] order
+struct CameraRaysArgs {
+    double camera[3];
+    uint64_t start_column, start_row, tile_width, tile_height;
+    uint64_t width, height;
+    uint64_t seed_key, first_sample;
+    uint32_t spp, pad;
+    double film[4];              // as RenderArgs::film
+    double* origins;             // [spp][tile pixels][3]
+    double* directions;          // [spp][tile pixels][3]
+    uint64_t* stream_ids;        // [spp][tile pixels]
+};
+
 // counters[] slots of the counting kernel variant
 enum Counter : int {
     kCntBoxTests = 0,
@@ -301,6 +333,15 @@ int launch_trace(const TraceArgs& args, int stack_depth, void* stream);
 // needs (the 4-wide tree's, or the binary tree's with VR_QUERY_REFERENCE_WALK); at most grid_limit
 // workgroups (grid-stride beyond).  Only enqueues.  -1000: deeper than the largest stack class
 int launch_query(const QueryArgs& args, int stack_depth, int grid_limit, void* stream);
+// vr_integrate.hip: one path per ray of args.n rays; stack_depth: the 4-wide tree's LDS stack entries;
+// at most grid_limit workgroups (each lane takes a grid-stride sequence of rays).  Only enqueues.
+// -1000: deeper than the largest stack class
+int launch_integrate(const IntegrateArgs& args, int stack_depth, int grid_limit, void* stream);
+int launch_camera_rays(const CameraRaysArgs& args, void* stream);
+// vr_render.hip: the ordered reduce alone -- update_pixel of photons[s * npix + p], s < spp, into the
+// records at `state` (RenderArgs::state's layout), no cull mask
+int launch_accumulate(double* state, const double* photons, uint64_t npix, uint32_t spp, uint32_t accumulate,
+                      void* stream);
 #ifdef VR_SPLIT_PROBE  // analysis builds (vr_render.hip)
 int launch_trace_probe(const RenderArgs& args, int stack_depth, int minw, bool s16, int grid, void* stream);
 #endif

@@ -1937,6 +1937,21 @@ static hipError_t launch_reduce(const RenderArgs& a, hipStream_t s, hipEvent_t m
     return hipGetLastError();
 }
 
+// the ordered reduce on its own, for photons a caller staged (vr_accumulate_photons_device): every
+// pixel's samples are read, there is no cull mask
+int launch_accumulate(double* state, const double* photons, uint64_t npix, uint32_t spp, uint32_t accumulate,
+                      void* stream) {
+#ifdef VR_STAGE_GUARD  // debug builds: caller-staged photons carry no generation tags
+    return (int)hipErrorNotSupported;
+#else
+    if (npix == 0) return 0;
+    hipLaunchKernelGGL(dev::accumulate_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       state, photons, npix, spp, accumulate, (const uint8_t*)nullptr, npix,
+                       (const uint32_t*)nullptr, 0u, (int32_t*)nullptr);
+    return (int)hipGetLastError();
+#endif
+}
+
 template <int STACK>
 static hipError_t launch_render_t(const RenderArgs& a, const LaunchChoice& c, int grid_limit, hipStream_t s,
                                   hipEvent_t mid) {

@@ -27,7 +27,10 @@ HIT_RECORD_DTYPE = np.dtype([("valid", "<i4"), ("object", "<i4"), ("primitive", 
                              ("cotangent", "<f8", (3,)), ("retro", "<f8", (3,))])
 RAY_HIT_DTYPE = np.dtype([("distance", "<f8"), ("primitive", "<i8"), ("object", "<i4"), ("valid", "<i4"),
                           ("reserved", "<u8")])
+PHOTON_DTYPE = np.dtype([("wavelength", "<f8"), ("intensity", "<f8")])
+PATH_INFO_DTYPE = np.dtype([("bounces", "<i4"), ("flags", "<i4")])
 assert RAY_HIT_DTYPE.itemsize == C.sizeof(N.RayHit) == 32
+assert PHOTON_DTYPE.itemsize == C.sizeof(N.Photon) == 16 and PATH_INFO_DTYPE.itemsize == C.sizeof(N.PathInfo) == 8
 assert SAMPLE_RECORD_DTYPE.itemsize == C.sizeof(N.SampleRecord)
 assert HIT_RECORD_DTYPE.itemsize == C.sizeof(N.HitRecord)
 
@@ -303,6 +306,72 @@ def query_any_device(scene, n, origins_ptr, directions_ptr, hit_ptr, stream_ptr=
     N.check(N.lib().vr_query_any_device(ds.handle, n, C.c_void_p(origins_ptr), C.c_void_p(directions_ptr),
                                         _query_flags(normalize, reference_walk), C.c_void_p(hit_ptr),
                                         C.c_void_p(stream_ptr or 0)))
+
+
+def _integrate_params(seed, first_stream, sample, first_draw, normalize):
+    return N.IntegrateParams(seed, first_stream, sample, first_draw, N.QUERY_NORMALIZE if normalize else 0)
+
+
+def integrate_rays(scene, origins, directions, seed, wavelengths=None, stream_ids=None, first_stream=0, sample=0,
+                   first_draw=0, normalize=False, info=False, device=0):
+    """The scene's integrator for a batch of host rays (vr_integrate_rays): one photon per ray as a
+    PHOTON_DTYPE array, or (photons, PATH_INFO_DTYPE info) with `info`.  `wavelengths`: one per ray, or
+    None to draw Photon::random_wavelength from the ray's stream; ray i draws from the stream
+    stream_ids[i] = (pixel << 32) + sample, or ((first_stream + i) << 32) + sample, skipping its first
+    `first_draw` draws.  Raises VrError(VR_ERROR_SINGULAR_BASIS) like a render."""
+    ds = _scene_handle(scene, device)
+    o, d = _rays(origins, directions)
+    n = len(o)
+    wl = ids = None
+    if wavelengths is not None:
+        wl = np.ascontiguousarray(wavelengths, dtype=np.float64).reshape(-1)
+        if len(wl) != n:
+            raise ValueError("wavelengths and rays differ in length")
+    if stream_ids is not None:
+        ids = np.ascontiguousarray(stream_ids, dtype=np.uint64).reshape(-1)
+        if len(ids) != n:
+            raise ValueError("stream_ids and rays differ in length")
+    photons = np.zeros(n, dtype=PHOTON_DTYPE)
+    inf = np.zeros(n, dtype=PATH_INFO_DTYPE) if info else None
+    p = _integrate_params(seed, first_stream, sample, first_draw, normalize)
+    N.check(N.lib().vr_integrate_rays(ds.handle, n, o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p),
+                                      wl.ctypes.data_as(C.c_void_p) if wl is not None else None,
+                                      ids.ctypes.data_as(C.c_void_p) if ids is not None else None, C.byref(p),
+                                      photons.ctypes.data_as(C.c_void_p),
+                                      inf.ctypes.data_as(C.c_void_p) if info else None))
+    return (photons, inf) if info else photons
+
+
+def integrate_rays_device(scene, n, origins_ptr, directions_ptr, photons_ptr, seed, wavelengths_ptr=None,
+                          stream_ids_ptr=None, info_ptr=None, first_stream=0, sample=0, first_draw=0, normalize=False,
+                          stream_ptr=None, device=0):
+    """Enqueue the scene's integrator for n rays in device memory ([n][3] f64 each) into device
+    vr_photon records at `photons_ptr` (and vr_path_info at `info_ptr`) on a stream; no
+    synchronisation.  A singular shading basis is reported by stream_check_error on that stream."""
+    ds = _scene_handle(scene, device)
+    p = _integrate_params(seed, first_stream, sample, first_draw, normalize)
+    N.check(N.lib().vr_integrate_rays_device(ds.handle, n, C.c_void_p(origins_ptr), C.c_void_p(directions_ptr),
+                                             C.c_void_p(wavelengths_ptr or 0), C.c_void_p(stream_ids_ptr or 0),
+                                             C.byref(p), C.c_void_p(photons_ptr), C.c_void_p(info_ptr or 0),
+                                             C.c_void_p(stream_ptr or 0)))
+
+
+def accumulate_photons_device(state_ptr, photons_ptr, pixel_count, spp, accumulate=False, stream_ptr=None, device=0):
+    """Enqueue update_pixel of device photons [spp][pixel_count] (sample-major, the staging layout) into
+    device state records at `state_ptr` (render_tile_device's layout): the render's ordered reduce alone."""
+    N.check(N.lib().vr_accumulate_photons_device(C.c_void_p(state_ptr), C.c_void_p(photons_ptr), pixel_count, spp,
+                                                 1 if accumulate else 0, device, C.c_void_p(stream_ptr or 0)))
+
+
+def camera_rays_device(scene, tile: Tile, height, width, spp, seed, first_sample, origins_ptr, directions_ptr,
+                       stream_ids_ptr, stream_ptr=None, device=0):
+    """Enqueue ImageSampler::ray_for_pixel of the scene's camera for every (sample, pixel) of `tile`
+    into device arrays of spp * tile pixels entries ([s][p] order): origins and directions ([.][3] f64)
+    and the samples' stream ids (u64), as integrate_rays_device takes them (first_draw=2)."""
+    ds = _scene_handle(scene, device)
+    p = _params(tile, height, width, spp, seed, first_sample, False)
+    N.check(N.lib().vr_camera_rays_device(ds.handle, C.byref(p), C.c_void_p(origins_ptr), C.c_void_p(directions_ptr),
+                                          C.c_void_p(stream_ids_ptr), C.c_void_p(stream_ptr or 0)))
 
 
 def render_tile_device(scene, tile: Tile, height, width, spp, seed, first_sample, state_ptr, stream_ptr=None,
