@@ -14,8 +14,12 @@
  *   - Return value: VR_OK (0) or a negative vr_status.  The message of the last failure on the
  *     calling thread is in vr_last_error().  Nothing unwinds across the ABI; where the reference
  *     panics (singular shading basis, out-of-range tile) the call returns an error instead.
- *   - A vr_scene is immutable after creation and may be shared by any number of threads;
- *     render calls are re-entrant.  Each call holds its own stream, staging buffer, work-queue
+ *   - A vr_scene changes only through vr_scene_update_mesh (new vertices for one mesh, VR_HAS_SCENE_UPDATE)
+ *     and the set-before-rendering hooks; between such calls it is immutable and may be shared by any
+ *     number of threads.  An update is not thread-safe against any other call on the same scene, and
+ *     asynchronous work of the scene still queued on any stream must have finished first (the
+ *     caller's to order, as for vr_scene_set_staging_limit).
+ *     Render calls are re-entrant.  Each call holds its own stream, staging buffer, work-queue
  *     counter and device error word for its duration (a per-scene pool of call contexts), so
  *     concurrent calls neither serialise on shared scratch nor see each other's errors
  *     (tests/test_gpu_concurrency.py).
@@ -213,6 +217,54 @@ int vr_scene_bvh_leaf_order(const vr_scene* scene, uint32_t mesh, uint64_t* out)
  * max z); int32 child[2] (>= 0 interior node, < 0 leaf holding triangle ~child); 24 B pad }.
  * For inspection and build-parity tests. */
 int vr_scene_bvh_nodes(const vr_scene* scene, void* out_nodes);
+
+/* ---------------------------------------------------------------------------------------------
+ * Scene updates: move or deform a mesh between frames without vr_scene_destroy + vr_scene_create.
+ * Added under ABI 10 (VR_HAS_SCENE_UPDATE).
+ *
+ * The mesh's triangle and normal records are replaced and both trees (the binary tree of
+ *   vr_trace_rays, shadow rays and VR_QUERY_REFERENCE_WALK, and the 4-wide render tree) are refitted
+ *   bottom-up and exactly, with the mesh's root box, vr_scene_info::extent (and the cull margins
+ *   derived from it) and VR_SCENE_INFO_NAN_FREE (and the early stop and kernel choice that follow
+ *   from it).  Topology, ranks, leaf order, node counts, stack depths, the pass counter, the staging
+ *   limit, the debug hooks, the pooled call contexts and the scene's device allocation stay.
+ * Afterwards every entry point behaves as on a scene created from the new geometry with the same
+ *   flags, bit for bit: the closest hit does not depend on the tree's shape, only on each triangle's
+ *   own box and its mesh's root box, which a refit stores exactly.  The one exception: exact
+ *   distance ties between two triangles of a mesh are broken by the rank in the reference's
+ *   median-split tree, and an update keeps the creation-time ranks where a fresh scene would re-rank.
+ *   A refitted tree may be slower to traverse than a rebuilt one (tools/update_bench.py reports it).
+ * Both calls block: when they return VR_OK the scene is ready and the source arrays may be freed.
+ * Errors come before anything is modified (a failed update leaves the scene bit for bit as it was):
+ *   a null scene or array, a bad mesh index or a triangle_count that is not the mesh's:
+ *   VR_ERROR_INVALID_ARGUMENT; a vertex coordinate that is not finite: VR_ERROR_UNSUPPORTED (normals
+ *   may be anything; zero normals clear NAN_FREE); the device form on a VR_SCENE_HOST_ONLY scene:
+ *   VR_ERROR_HOST_ONLY.  triangle_count == 0 on an empty mesh is VR_OK.  A mesh that backs no object
+ *   is updated like any other.
+ * On a VR_SCENE_HOST_ONLY scene the host form runs the same refit in plain C++ on the host arrays,
+ *   with no device call.
+ * The first update of a mesh builds its plan (slot -> input triangle, both trees' nodes by depth),
+ *   kept in the scene; its bytes are added to vr_scene_info::device_bytes.
+ * --------------------------------------------------------------------------------------------- */
+#define VR_HAS_SCENE_UPDATE 1
+/* new vertices / normals for mesh `mesh` (index into vr_scene_desc::meshes), [triangle][corner][xyz] f64 as
+ * vr_mesh_desc; triangle_count must equal the mesh's.  Host arrays. */
+int vr_scene_update_mesh(vr_scene* scene, uint32_t mesh, uint64_t triangle_count, const double* vertices,
+                         const double* normals);
+/* the same from device arrays on the scene's GPU, ordered after earlier work on `stream` (NULL = the null stream) */
+int vr_scene_update_mesh_device(vr_scene* scene, uint32_t mesh, uint64_t triangle_count, const double* vertices,
+                                const double* normals, void* stream);
+/* Inspection, beside vr_scene_bvh_nodes (all four: always the current state; device scenes read back).
+ * vr_scene_wide_nodes: wide_node_count records of 128 B = { float bound[6][4] (min x, max x, min y,
+ *   max y, min z, max z of the four child slots; NaN: empty); int32 child[4] (>= 0 wide node, INT32_MIN
+ *   empty, else leaf holding triangle slot ~child); 16 B pad }.
+ * vr_scene_triangles: triangle_count records of 80 B each, in slot (traversal leaf) order:
+ *   { double v[9]; int64 rank } and { double n[9]; 8 B pad }; a NULL array is skipped.
+ * vr_scene_bvh_roots: one 96-B record per BVH object, in object order = { double root_box[6];
+ *   float root_box32[6]; int32 root, root4, pad, object, tri_base, material }. */
+int vr_scene_wide_nodes(const vr_scene* scene, void* out);
+int vr_scene_triangles(const vr_scene* scene, void* out_verts, void* out_normals);
+int vr_scene_bvh_roots(const vr_scene* scene, void* out);
 
 /* util::Tile (src/util/tile_iterator.rs:1-7): half-open row/column ranges of the full image. */
 typedef struct vr_tile {

@@ -169,6 +169,11 @@ SIGNATURES = {
     "vr_scene_get_info": (C.c_int, [_p, C.POINTER(SceneInfo)]),
     "vr_scene_bvh_leaf_order": (C.c_int, [_p, _u32, _p]),
     "vr_scene_bvh_nodes": (C.c_int, [_p, _p]),
+    "vr_scene_update_mesh": (C.c_int, [_p, _u32, _u64, _p, _p]),
+    "vr_scene_update_mesh_device": (C.c_int, [_p, _u32, _u64, _p, _p, _p]),
+    "vr_scene_wide_nodes": (C.c_int, [_p, _p]),
+    "vr_scene_triangles": (C.c_int, [_p, _p, _p]),
+    "vr_scene_bvh_roots": (C.c_int, [_p, _p]),
     "vr_partial_render_scene": (C.c_int, [_p, TileC, _u64, _u64, C.POINTER(AccumulationBufferC)]),
     "vr_render_tile": (C.c_int, [_p, C.POINTER(RenderParams), C.POINTER(AccumulationBufferC)]),
     "vr_render_tile_device": (C.c_int, [_p, C.POINTER(RenderParams), _p, _p, _u32, C.POINTER(LaunchStats)]),

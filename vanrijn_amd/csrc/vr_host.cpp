@@ -35,6 +35,7 @@
 #include "../../include/vanrijn_amd.h"
 #include "rgb_spectrum_tables.h"
 #include "vr_layout.h"
+#include "vr_refit.h"
 
 #include <zlib.h>
 
@@ -588,6 +589,32 @@ struct vr_scene {
     int32_t fault_object = -1;
     // test hook (vr_debug_set_launch_flags): launch flags OR'ed into every render of the scene
     uint32_t debug_launch_flags = 0;
+    // vr_scene_update_mesh: the parts extent, NAN_FREE and dark0 are put together from
+    // (update_scalars), where each mesh's records are, and the per-mesh plans
+    double base_extent = 0.0;             // camera and primitives
+    std::vector<double> mesh_extent;      // max |coordinate| of each mesh
+    std::vector<uint8_t> mesh_finite;     // shading_finite of each mesh (1 where no object traces it)
+    bool dark0_materials = true;          // dark0's materials-only part
+    std::vector<int> mesh_object;         // the BVH object a mesh backs, or -1
+    std::vector<int> mesh_bvh;            // its record in bvhs, or -1
+    std::vector<int32_t> mesh_node_base;  // its first interior node (the root of a mesh of 2 or more triangles)
+    std::vector<int32_t> mesh_root4;      // its 4-wide root node, or kEmptyChild
+    bool host_stale = false;  // a device update ran: the host copies of trees and triangles are the creation's
+    struct UpdatePlan {
+        bool built = false;
+        std::vector<uint32_t> slot_src;       // per slot of the mesh: the input triangle it holds
+        std::vector<int32_t> items2, items4;  // node indices of the binary / 4-wide tree grouped by depth
+        std::vector<uint32_t> first2, first4; // items[first[l] .. first[l + 1]): depth l (root 0)
+        // device copy: [Validation | slot_src | items2 | items4], and the host form's uploaded arrays
+        void* d_plan = nullptr;
+        size_t plan_bytes = 0;
+        unsigned long long* d_valid = nullptr;
+        uint32_t* d_slot_src = nullptr;
+        int32_t *d_items2 = nullptr, *d_items4 = nullptr;
+        void* d_stage = nullptr;
+        size_t stage_bytes = 0;
+    };
+    std::vector<UpdatePlan> plans;
 };
 
 // The render kernel addresses the triangle and 4-wide node arrays with 32-bit byte offsets from
@@ -794,6 +821,22 @@ namespace {
 int stack_depth(const vr_scene* s) { return std::max(1, s->max_depth - 1); }  // binary tree walks
 int wide_stack_depth(const vr_scene* s) { return s->wide_stack + 1; }  // render kernel (+1: branchless pushes)
 
+// The scene scalars that depend on mesh geometry, from their per-mesh parts: at creation, and again
+// after vr_scene_update_mesh replaced one mesh's part -- so an updated scene holds a fresh scene's values.
+void update_scalars(vr_scene* s) {
+    double extent = s->base_extent;
+    for (double e : s->mesh_extent) extent = std::max(extent, e);
+    s->extent = extent;
+    s->dev.margin = 1e-9 * (extent + 1.0);
+    s->dev.behind_margin = 1e-6 * (extent + 1.0);
+    s->dev.extent = extent;
+    // NaN-capable continuations (shading_finite): no early stop, the general lambda-0 chain
+    s->nan_free = (s->mats & 4) == 0;
+    for (uint8_t f : s->mesh_finite)
+        if (!f) s->nan_free = false;
+    s->dark0 = s->dark0_materials && s->nan_free;
+}
+
 
 // the render kernel's 4-wide tree over every traversed mesh's binary tree `nodes`
 void collapse_wide(vr_scene* s, const std::vector<vr::Node>& nodes) {
@@ -953,6 +996,7 @@ int upload(vr_scene* s) {
             if (pm.n < 2) continue;  // one-triangle mesh: its root is the leaf
             W.tri_base = pm.tri_base;
             const int32_t root = W.wide({0, pm.n, pm.node_base}, 0);
+            s->mesh_root4[pm.mesh] = root;
             for (auto& b : s->bvhs)
                 if (b.tri_base == pm.tri_base && b.root == pm.node_base) b.root4 = root;
         }
@@ -1495,13 +1539,21 @@ int vr_scene_create(const vr_scene_desc* desc, int32_t device, uint32_t flags, v
     }
     s->object_count = desc->object_count;
     // NaN-capable continuations (shading_finite): no early stop, the general lambda-0 chain
-    if (s->mats & 4) s->nan_free = false;
-    for (uint32_t mi = 0; mi < desc->mesh_count && s->nan_free; ++mi) {
+    // (one result per mesh, every mesh evaluated: vr_scene_update_mesh replaces one of them)
+    s->mesh_finite.assign(desc->mesh_count, 1);
+    for (uint32_t mi = 0; mi < desc->mesh_count; ++mi) {
         const vr_mesh_desc& m = desc->meshes[mi];
         if (mesh_object[mi] >= 0 && m.triangle_count && m.vertices && m.normals && !shading_finite(m))
-            s->nan_free = false;
+            s->mesh_finite[mi] = 0;
     }
-    if (!s->nan_free) s->dark0 = false;
+    s->dark0_materials = s->dark0;
+    s->base_extent = extent;
+    s->mesh_extent.assign(desc->mesh_count, 0.0);
+    s->mesh_object = mesh_object;
+    s->mesh_bvh.assign(desc->mesh_count, -1);
+    s->mesh_node_base.assign(desc->mesh_count, 0);
+    s->mesh_root4.assign(desc->mesh_count, vr::kEmptyChild);
+    s->plans.resize(desc->mesh_count);
     s->leaf_order.resize(desc->mesh_count);
     s->mesh_tri_base.assign(desc->mesh_count, 0);
     // device build: requested, a device exists for it, and no NaN coordinate (the reference's
@@ -1538,7 +1590,7 @@ int vr_scene_create(const vr_scene_desc* desc, int32_t device, uint32_t flags, v
                     for (int c = 0; c < 3; ++c) {
                         const double v = m.vertices[9 * t + 3 * k + c];
                         bb.b[c] = iv_expand(bb.b[c], v);
-                        extent = std::max(extent, std::fabs(v));
+                        s->mesh_extent[mi] = std::max(s->mesh_extent[mi], std::fabs(v));
                     }
                 rb = box_union(rb, bb);
             }
@@ -1552,6 +1604,7 @@ int vr_scene_create(const vr_scene_desc* desc, int32_t device, uint32_t flags, v
                 s->max_depth = std::max(s->max_depth, 1);
             }
             s->leaf_order[mi].assign(m.triangle_count, 0);
+            s->mesh_node_base[mi] = (int32_t)s->node_count;
             s->node_count += m.triangle_count ? m.triangle_count - 1 : 0;
             s->tri_count += m.triangle_count;
             if (mesh_object[mi] >= 0) s->bvhs.push_back(bvh);
@@ -1568,7 +1621,7 @@ int vr_scene_create(const vr_scene_desc* desc, int32_t device, uint32_t flags, v
                 for (int c = 0; c < 3; ++c) {
                     double v = m.vertices[9 * t + 3 * k + c];
                     bb.b[c] = iv_expand(bb.b[c], v);
-                    extent = std::max(extent, std::fabs(v));
+                    s->mesh_extent[mi] = std::max(s->mesh_extent[mi], std::fabs(v));
                 }
             B.prims[t].box = bb;
             for (int c = 0; c < 3; ++c) B.prims[t].centre[c] = (bb.b[c].min + bb.b[c].max) / 2.0;  // centre()
@@ -1578,6 +1631,7 @@ int vr_scene_create(const vr_scene_desc* desc, int32_t device, uint32_t flags, v
         bvh.object = mesh_object[mi];
         bvh.tri_base = B.tri_base;
         bvh.material = (int32_t)m.material;
+        s->mesh_node_base[mi] = (int32_t)s->nodes.size();
         if (m.triangle_count == 0) {
             bvh.root = INT32_MIN;
             for (int i = 0; i < 6; ++i) bvh.root_box[i] = (i & 1) ? -INFINITY : INFINITY;
@@ -1634,14 +1688,11 @@ int vr_scene_create(const vr_scene_desc* desc, int32_t device, uint32_t flags, v
     std::sort(s->bvhs.begin(), s->bvhs.end(), [](const vr::Bvh& a, const vr::Bvh& b) { return a.object < b.object; });
     // the render kernel's 4-wide tree (device builds: after the build, in upload)
     if (!s->device_bvh) collapse_wide(s, s->nodes);
-    s->extent = extent;
     vr::DeviceScene& d = s->dev;
     d.prim_count = (int32_t)s->prims.size();
     d.bvh_count = (int32_t)s->bvhs.size();
     std::memcpy(d.camera, s->camera, sizeof d.camera);
-    d.margin = 1e-9 * (extent + 1.0);
-    d.behind_margin = 1e-6 * (extent + 1.0);
-    d.extent = extent;
+    update_scalars(s);  // extent and the margins, NAN_FREE, dark0
     if (!s->host_only) {
         int rc = upload(s);
         if (rc != VR_OK) {
@@ -1650,6 +1701,12 @@ int vr_scene_create(const vr_scene_desc* desc, int32_t device, uint32_t flags, v
             return fail(rc, msg);
         }
     }
+    for (uint32_t mi = 0; mi < desc->mesh_count; ++mi)
+        for (size_t bi = 0; bi < s->bvhs.size(); ++bi)
+            if (mesh_object[mi] >= 0 && s->bvhs[bi].object == mesh_object[mi]) {
+                s->mesh_bvh[mi] = (int)bi;
+                s->mesh_root4[mi] = s->bvhs[bi].root4 >= 0 ? s->bvhs[bi].root4 : vr::kEmptyChild;
+            }
     *out = s;
     return VR_OK;
 }
@@ -1661,6 +1718,10 @@ void vr_scene_destroy(vr_scene* s) {
         for (CallCtx* c : s->ctx_all) ctx_free_all(c);  // waits for each context's last work
         // (the streams may be gone by now: hipFree waits for the device instead)
         for (auto& kv : s->stream_slots) (void)hipFree(kv.second);
+        for (auto& p : s->plans) {
+            if (p.d_plan) (void)hipFree(p.d_plan);
+            if (p.d_stage) (void)hipFree(p.d_stage);
+        }
         if (s->d_block) (void)hipFree(s->d_block);
     }
     for (auto& kv : s->deferred)
@@ -1713,7 +1774,7 @@ int vr_scene_bvh_nodes(const vr_scene* s, void* out) {
     if (!s || !out) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
     const size_t bytes = s->node_count * sizeof(vr::Node);
     if (bytes == 0) return VR_OK;
-    if (!s->device_bvh) {
+    if (!s->device_bvh && !s->host_stale) {
         std::memcpy(out, s->nodes.data(), bytes);
         return VR_OK;
     }
@@ -1725,6 +1786,276 @@ int vr_scene_bvh_nodes(const vr_scene* s, void* out) {
 int vr_scene_bvh_leaf_order(const vr_scene* s, uint32_t mesh, uint64_t* out) {
     if (!s || !out || mesh >= s->leaf_order.size()) return fail(VR_ERROR_INVALID_ARGUMENT, "bad mesh index");
     std::memcpy(out, s->leaf_order[mesh].data(), sizeof(uint64_t) * s->leaf_order[mesh].size());
+    return VR_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// vr_scene_update_mesh: new vertices for one mesh, both trees refitted in place (vr_refit.h holds
+// the per-record steps, vr_refit.hip the device stages)
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// whether the host vectors (nodes, nodes4, tris, normals) hold the scene's current state
+bool host_copies_current(const vr_scene* s) { return s->host_only || (!s->device_bvh && !s->host_stale); }
+
+// The plan of mesh `mi`, built at its first update: which input triangle every slot holds (from the
+// ranks in the slots and the leaf order) and both trees' node indices grouped by depth, found by
+// walking the child links from the roots.  Device-built scenes keep no host copy of the trees, so
+// their links are read back here, once.  Every index is range-checked: the kernels trust the plan.
+int build_update_plan(vr_scene* s, uint32_t mi) {
+    vr_scene::UpdatePlan& p = s->plans[mi];
+    const uint64_t n = s->leaf_order[mi].size(), interior = n ? n - 1 : 0;
+    const int64_t tri_base = s->mesh_tri_base[mi], node_base = s->mesh_node_base[mi];
+    const bool readback = !s->host_only && s->device_bvh;
+    std::vector<vr::TriVerts> tv;
+    std::vector<vr::Node> bn;
+    std::vector<vr::Node4> wn;
+    if (readback) {
+        tv.resize(n);
+        bn.resize(interior);
+        wn.resize(s->wide_count);
+        VR_HIP(hipMemcpy(tv.data(), s->dev.tris + tri_base, n * sizeof(vr::TriVerts), hipMemcpyDeviceToHost));
+        if (interior)
+            VR_HIP(hipMemcpy(bn.data(), s->dev.nodes + node_base, interior * sizeof(vr::Node), hipMemcpyDeviceToHost));
+        if (s->wide_count)
+            VR_HIP(hipMemcpy(wn.data(), s->dev.nodes4, s->wide_count * sizeof(vr::Node4), hipMemcpyDeviceToHost));
+    }
+    const vr::TriVerts* tris = readback ? tv.data() : s->tris.data() + tri_base;      // the mesh's slots
+    const vr::Node* nodes = readback ? bn.data() : s->nodes.data() + node_base;        // the mesh's nodes
+    const vr::Node4* nodes4 = readback ? wn.data() : s->nodes4.data();                 // every wide node
+    const uint64_t wide_count = readback ? wn.size() : s->nodes4.size();
+    const char* corrupt = "scene update: the tree's links do not form the mesh's tree";
+    p.slot_src.resize(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        const int64_t r = tris[i].rank - tri_base;
+        if (r < 0 || (uint64_t)r >= n || s->leaf_order[mi][(size_t)r] >= n) return fail(VR_ERROR_DEVICE, corrupt);
+        p.slot_src[i] = (uint32_t)s->leaf_order[mi][(size_t)r];
+    }
+    auto leaf_ok = [&](int32_t ch) { return (int64_t)~ch >= tri_base && (uint64_t)((int64_t)~ch - tri_base) < n; };
+    p.items2.clear();
+    p.first2.assign(1, 0);
+    std::vector<int32_t> frontier, next;
+    if (n >= 2) frontier.push_back((int32_t)node_base);
+    while (!frontier.empty()) {
+        next.clear();
+        for (int32_t x : frontier) {
+            p.items2.push_back(x);
+            for (int c = 0; c < 2; ++c) {
+                const int32_t ch = nodes[x - node_base].child[c];
+                if (ch >= 0) {
+                    if (ch < node_base || (uint64_t)(ch - node_base) >= interior) return fail(VR_ERROR_DEVICE, corrupt);
+                    next.push_back(ch);
+                } else if (!leaf_ok(ch)) {
+                    return fail(VR_ERROR_DEVICE, corrupt);
+                }
+            }
+        }
+        if (p.items2.size() + next.size() > interior) return fail(VR_ERROR_DEVICE, corrupt);  // a cycle
+        p.first2.push_back((uint32_t)p.items2.size());
+        frontier.swap(next);
+    }
+    p.items4.clear();
+    p.first4.assign(1, 0);
+    frontier.clear();
+    if (s->mesh_root4[mi] != vr::kEmptyChild) {
+        if ((uint64_t)s->mesh_root4[mi] >= wide_count) return fail(VR_ERROR_DEVICE, corrupt);
+        frontier.push_back(s->mesh_root4[mi]);
+    }
+    while (!frontier.empty()) {
+        next.clear();
+        for (int32_t x : frontier) {
+            p.items4.push_back(x);
+            for (int c = 0; c < 4; ++c) {
+                const int32_t ch = nodes4[x].child[c];
+                if (ch == vr::kEmptyChild) continue;
+                if (ch >= 0) {
+                    if ((uint64_t)ch >= wide_count) return fail(VR_ERROR_DEVICE, corrupt);
+                    next.push_back(ch);
+                } else if (!leaf_ok(ch)) {
+                    return fail(VR_ERROR_DEVICE, corrupt);
+                }
+            }
+        }
+        if (p.items4.size() + next.size() > wide_count) return fail(VR_ERROR_DEVICE, corrupt);
+        p.first4.push_back((uint32_t)p.items4.size());
+        frontier.swap(next);
+    }
+    if (!s->host_only) {
+        auto a16 = [](size_t b) { return (b + 15) & ~size_t(15); };
+        const size_t o_src = a16(sizeof(vr::refit::Validation)), o_i2 = o_src + a16(4 * n),
+                     o_i4 = o_i2 + a16(4 * p.items2.size()), total = o_i4 + a16(4 * p.items4.size());
+        VR_HIP(hipMalloc(&p.d_plan, total));
+        p.plan_bytes = total;
+        s->device_bytes += total;
+        char* b = (char*)p.d_plan;
+        p.d_valid = (unsigned long long*)b;
+        p.d_slot_src = (uint32_t*)(b + o_src);
+        p.d_items2 = (int32_t*)(b + o_i2);
+        p.d_items4 = (int32_t*)(b + o_i4);
+        if (n) VR_HIP(hipMemcpy(p.d_slot_src, p.slot_src.data(), 4 * n, hipMemcpyHostToDevice));
+        if (!p.items2.empty()) VR_HIP(hipMemcpy(p.d_items2, p.items2.data(), 4 * p.items2.size(), hipMemcpyHostToDevice));
+        if (!p.items4.empty()) VR_HIP(hipMemcpy(p.d_items4, p.items4.data(), 4 * p.items4.size(), hipMemcpyHostToDevice));
+    }
+    p.built = true;
+    return VR_OK;
+}
+
+// the refit in plain C++ on the host arrays (VR_SCENE_HOST_ONLY): the steps of vr_refit.hip in its order
+int update_mesh_host(vr_scene* s, uint32_t mi, uint64_t n, const double* verts, const double* norms) {
+    vr::refit::Validation val{};
+    double max_abs = 0.0;
+    for (uint64_t t = 0; t < n; ++t) {
+        for (int i = 0; i < 9; ++i) {
+            if (!std::isfinite(verts[9 * t + i])) ++val.nonfinite;
+            max_abs = std::max(max_abs, std::fabs(verts[9 * t + i]));
+        }
+        if (!vr::refit::tri_shading_finite(verts + 9 * t, norms + 9 * t)) ++val.not_finite;
+    }
+    if (val.nonfinite) return fail(VR_ERROR_UNSUPPORTED, "scene update: a vertex coordinate is not finite");
+    vr_scene::UpdatePlan& p = s->plans[mi];
+    if (!p.built) {
+        const int rc = build_update_plan(s, mi);
+        if (rc) return rc;
+    }
+    const int32_t tri_base = s->mesh_tri_base[mi];
+    for (uint64_t i = 0; i < n; ++i) {
+        std::memcpy(s->tris[tri_base + i].v, verts + 9 * (uint64_t)p.slot_src[i], 9 * sizeof(double));
+        std::memcpy(s->normals[tri_base + i].n, norms + 9 * (uint64_t)p.slot_src[i], 9 * sizeof(double));
+    }
+    for (size_t l = p.first2.size() - 1; l-- > 0;)
+        for (uint32_t k = p.first2[l]; k < p.first2[l + 1]; ++k)
+            vr::refit::refit_node(s->nodes.data(), s->tris.data(), p.items2[k]);
+    for (size_t l = p.first4.size() - 1; l-- > 0;)
+        for (uint32_t k = p.first4[l]; k < p.first4[l + 1]; ++k)
+            vr::refit::refit_node4(s->nodes4.data(), s->tris.data(), p.items4[k]);
+    if (s->mesh_bvh[mi] >= 0) vr::refit::refit_root(&s->bvhs[s->mesh_bvh[mi]], s->nodes.data(), s->tris.data());
+    s->mesh_extent[mi] = max_abs;
+    s->mesh_finite[mi] = s->mesh_object[mi] < 0 || val.not_finite == 0;
+    update_scalars(s);
+    return VR_OK;
+}
+
+// ... and on the device; `device_arrays`: verts / norms are device pointers, else they are uploaded first
+int update_mesh_device(vr_scene* s, uint32_t mi, uint64_t n, const double* verts, const double* norms,
+                       bool device_arrays, hipStream_t st) {
+    VR_HIP(hipSetDevice(s->device));
+    vr_scene::UpdatePlan& p = s->plans[mi];
+    if (!p.built) {
+        const int rc = build_update_plan(s, mi);
+        if (rc) return rc;
+    }
+    const size_t row_bytes = (size_t)n * 9 * sizeof(double);
+    if (!device_arrays) {
+        if (p.stage_bytes < 2 * row_bytes) {
+            if (p.d_stage) VR_HIP(hipFree(p.d_stage));
+            s->device_bytes -= p.stage_bytes;
+            p.d_stage = nullptr;
+            p.stage_bytes = 0;
+            VR_HIP(hipMalloc(&p.d_stage, 2 * row_bytes));
+            p.stage_bytes = 2 * row_bytes;
+            s->device_bytes += p.stage_bytes;
+        }
+        VR_HIP(hipMemcpyAsync(p.d_stage, verts, row_bytes, hipMemcpyHostToDevice, st));
+        VR_HIP(hipMemcpyAsync((char*)p.d_stage + row_bytes, norms, row_bytes, hipMemcpyHostToDevice, st));
+        verts = (const double*)p.d_stage;
+        norms = (const double*)((const char*)p.d_stage + row_bytes);
+    }
+    auto dev = [](int e, const char* what) {
+        return fail(VR_ERROR_DEVICE, std::string(what) + ": " + hipGetErrorString((hipError_t)e));
+    };
+    // errors come before anything is modified: the reduction over the new arrays is read back first
+    int e = vr::launch_refit_validate(verts, norms, n, p.d_valid, st);
+    if (e) return dev(e, "scene update (validate)");
+    vr::refit::Validation val{};
+    VR_HIP(hipMemcpyAsync(&val, p.d_valid, sizeof val, hipMemcpyDeviceToHost, st));
+    VR_HIP(hipStreamSynchronize(st));
+    if (val.nonfinite) return fail(VR_ERROR_UNSUPPORTED, "scene update: a vertex coordinate is not finite");
+    const int32_t tri_base = s->mesh_tri_base[mi];
+    vr::TriVerts* tris = const_cast<vr::TriVerts*>(s->dev.tris);
+    vr::Node* nodes = const_cast<vr::Node*>(s->dev.nodes);
+    e = vr::launch_refit_gather(verts, norms, p.d_slot_src, n, tris + tri_base,
+                                const_cast<vr::TriNormals*>(s->dev.normals) + tri_base, st);
+    if (e) return dev(e, "scene update (gather)");
+    e = vr::launch_refit_levels(nodes, nullptr, tris, p.d_items2, p.first2.data(), (uint32_t)p.first2.size() - 1, st);
+    if (e) return dev(e, "scene update (binary refit)");
+    if (!p.items4.empty()) {
+        e = vr::launch_refit_levels(nullptr, const_cast<vr::Node4*>(s->dev.nodes4), tris, p.d_items4, p.first4.data(),
+                                    (uint32_t)p.first4.size() - 1, st);
+        if (e) return dev(e, "scene update (4-wide refit)");
+    }
+    const int bi = s->mesh_bvh[mi];
+    if (bi >= 0) {
+        vr::Bvh* rec = const_cast<vr::Bvh*>(s->dev.bvhs) + bi;
+        e = vr::launch_refit_root(rec, nodes, tris, st);
+        if (e) return dev(e, "scene update (root)");
+        VR_HIP(hipMemcpyAsync(&s->bvhs[bi], rec, sizeof(vr::Bvh), hipMemcpyDeviceToHost, st));
+    }
+    VR_HIP(hipStreamSynchronize(st));
+    if (!s->device_bvh) s->host_stale = true;
+    double max_abs;
+    std::memcpy(&max_abs, &val.max_abs, sizeof max_abs);
+    s->mesh_extent[mi] = max_abs;
+    s->mesh_finite[mi] = s->mesh_object[mi] < 0 || val.not_finite == 0;
+    update_scalars(s);
+    return VR_OK;
+}
+
+int update_mesh_checked(vr_scene* s, uint32_t mesh, uint64_t n, const double* verts, const double* norms,
+                        bool device_arrays, void* stream) {
+    if (!s) return fail(VR_ERROR_INVALID_ARGUMENT, "null scene");
+    if (mesh >= s->leaf_order.size()) return fail(VR_ERROR_INVALID_ARGUMENT, "scene update: bad mesh index");
+    if (n != s->leaf_order[mesh].size())
+        return fail(VR_ERROR_INVALID_ARGUMENT, "scene update: triangle_count differs from the mesh's");
+    if (n && (!verts || !norms)) return fail(VR_ERROR_INVALID_ARGUMENT, "scene update: null vertex or normal array");
+    if (device_arrays && s->host_only) return fail(VR_ERROR_HOST_ONLY, "scene was created with VR_SCENE_HOST_ONLY");
+    if (n == 0) return VR_OK;  // an empty mesh stays empty
+    if (s->host_only) return update_mesh_host(s, mesh, n, verts, norms);
+    return update_mesh_device(s, mesh, n, verts, norms, device_arrays, (hipStream_t)stream);
+}
+
+}  // namespace
+
+int vr_scene_update_mesh(vr_scene* s, uint32_t mesh, uint64_t triangle_count, const double* vertices,
+                         const double* normals) {
+    return update_mesh_checked(s, mesh, triangle_count, vertices, normals, false, nullptr);
+}
+
+int vr_scene_update_mesh_device(vr_scene* s, uint32_t mesh, uint64_t triangle_count, const double* vertices,
+                                const double* normals, void* stream) {
+    return update_mesh_checked(s, mesh, triangle_count, vertices, normals, true, stream);
+}
+
+int vr_scene_wide_nodes(const vr_scene* s, void* out) {
+    if (!s || !out) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
+    const size_t bytes = s->wide_count * sizeof(vr::Node4);
+    if (bytes == 0) return VR_OK;
+    if (host_copies_current(s)) {
+        std::memcpy(out, s->nodes4.data(), bytes);
+        return VR_OK;
+    }
+    VR_HIP(hipSetDevice(s->device));
+    VR_HIP(hipMemcpy(out, s->dev.nodes4, bytes, hipMemcpyDeviceToHost));
+    return VR_OK;
+}
+
+int vr_scene_triangles(const vr_scene* s, void* out_verts, void* out_normals) {
+    if (!s) return fail(VR_ERROR_INVALID_ARGUMENT, "null scene");
+    const size_t bytes = s->tri_count * sizeof(vr::TriVerts);
+    if (bytes == 0) return VR_OK;
+    if (host_copies_current(s)) {
+        if (out_verts) std::memcpy(out_verts, s->tris.data(), bytes);
+        if (out_normals) std::memcpy(out_normals, s->normals.data(), bytes);
+        return VR_OK;
+    }
+    VR_HIP(hipSetDevice(s->device));
+    if (out_verts) VR_HIP(hipMemcpy(out_verts, s->dev.tris, bytes, hipMemcpyDeviceToHost));
+    if (out_normals) VR_HIP(hipMemcpy(out_normals, s->dev.normals, bytes, hipMemcpyDeviceToHost));
+    return VR_OK;
+}
+
+int vr_scene_bvh_roots(const vr_scene* s, void* out) {
+    if (!s || !out) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
+    std::memcpy(out, s->bvhs.data(), s->bvhs.size() * sizeof(vr::Bvh));
     return VR_OK;
 }
 

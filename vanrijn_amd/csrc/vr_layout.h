@@ -342,6 +342,19 @@ int launch_camera_rays(const CameraRaysArgs& args, void* stream);
 // records at `state` (RenderArgs::state's layout), no cull mask
 int launch_accumulate(double* state, const double* photons, uint64_t npix, uint32_t spp, uint32_t accumulate,
                       void* stream);
+// vr_refit.hip: the device stages of vr_scene_update_mesh; each only enqueues on `stream` and returns a
+// hipError_t (0: ok).
+// validate: `n` triangles' new arrays reduced into out4 (zeroed first; vr_refit.h refit::Validation)
+int launch_refit_validate(const double* verts, const double* norms, uint64_t n, unsigned long long* out4, void* stream);
+// gather: slot i < n of tris / normals takes input triangle slot_src[i]; its rank and padding stay
+int launch_refit_gather(const double* verts, const double* norms, const uint32_t* slot_src, uint64_t n, TriVerts* tris,
+                        TriNormals* normals, void* stream);
+// refit: one launch per level, deepest first; items (device): node indices grouped by depth,
+// host_first (host, levels + 1 entries): where each depth starts in it.  nodes4 != nullptr: the
+// 4-wide tree, else the binary tree
+int launch_refit_levels(Node* nodes, Node4* nodes4, const TriVerts* tris, const int32_t* items, const uint32_t* host_first,
+                        uint32_t levels, void* stream);
+int launch_refit_root(Bvh* bvh, const Node* nodes, const TriVerts* tris, void* stream);
 #ifdef VR_SPLIT_PROBE  // analysis builds (vr_render.hip)
 int launch_trace_probe(const RenderArgs& args, int stack_depth, int minw, bool s16, int grid, void* stream);
 #endif

@@ -1,0 +1,150 @@
+// vr_refit.hip -- the device stages of vr_scene_update_mesh (include/vanrijn_amd.h): new vertices for
+// one mesh of a resident scene, its two trees refitted in place.  Topology, ranks and leaf order stay;
+// only triangle records and boxes change.
+//
+//   validate   one pass over the caller's arrays: non-finite coordinates, max |coordinate| (the scene
+//              extent) and the shading_finite predicate (VR_SCENE_INFO_NAN_FREE), reduced into four
+//              words the host reads back before anything is modified
+//   gather     slot i of the mesh's TriVerts / TriNormals takes input triangle slot_src[i]
+//   refit      both trees bottom-up, ONE LAUNCH PER LEVEL, deepest first: a level reads only triangle
+//              records and nodes of deeper levels, which earlier launches of the stream wrote.  Kernel
+//              boundaries are the only synchronisation: no thread waits for another, and no
+//              workgroup consumes what another wrote in the same launch (that would need an
+//              agent-scope release / acquire per hand-off, and fail as a silently stale box).
+//   root       Bvh::root_box and root_box32 of the mesh's root record
+//
+// The per-record arithmetic lives in vr_refit.h, shared with the host refit of VR_SCENE_HOST_ONLY
+// scenes: min / max and outward rounding only, so the stored bits do not depend on who computed them.
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdint.h>
+
+#include "vr_layout.h"
+#include "vr_refit.h"
+
+namespace vr {
+namespace refit {
+
+constexpr int kBlock = 256;
+
+__global__ void __launch_bounds__(kBlock) validate_kernel(const double* __restrict__ verts, const double* __restrict__ norms,
+                                                          uint64_t n, Validation* out) {
+    unsigned long long nonfinite = 0, not_finite = 0;
+    double max_abs = 0.0;
+    for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < n; t += (uint64_t)gridDim.x * kBlock) {
+        double v[9], nn[9];
+        for (int i = 0; i < 9; ++i) {
+            v[i] = verts[9 * t + i];
+            nn[i] = norms[9 * t + i];
+        }
+        for (int i = 0; i < 9; ++i) {
+            if (!isfinite(v[i])) ++nonfinite;
+            const double a = fabs(v[i]);
+            max_abs = max_abs < a ? a : max_abs;  // std::max(extent, |v|): a NaN never replaces it
+        }
+        if (!tri_shading_finite(v, nn)) ++not_finite;
+    }
+    __shared__ unsigned long long s_bad[kBlock], s_nf[kBlock], s_max[kBlock];
+    s_bad[threadIdx.x] = nonfinite;
+    s_nf[threadIdx.x] = not_finite;
+    s_max[threadIdx.x] = (unsigned long long)__double_as_longlong(max_abs);  // >= 0: ordered as integers
+    __syncthreads();
+    for (int w = kBlock / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            s_bad[threadIdx.x] += s_bad[threadIdx.x + w];
+            s_nf[threadIdx.x] += s_nf[threadIdx.x + w];
+            s_max[threadIdx.x] = s_max[threadIdx.x] < s_max[threadIdx.x + w] ? s_max[threadIdx.x + w] : s_max[threadIdx.x];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if (s_bad[0]) atomicAdd(&out->nonfinite, s_bad[0]);
+        if (s_nf[0]) atomicAdd(&out->not_finite, s_nf[0]);
+        atomicMax(&out->max_abs, s_max[0]);
+    }
+}
+
+// Destination records are 80 B at 16-B alignment: five dwordx4 stores each.  The last quad of a
+// TriVerts holds v[8] and the rank, of a TriNormals n[8] and the padding: rank and padding are read
+// and stored back unchanged.  Source rows are 72 B at 8-B alignment (dwordx2 loads).
+__global__ void __launch_bounds__(kBlock) gather_kernel(const double* __restrict__ verts, const double* __restrict__ norms,
+                                                        const uint32_t* __restrict__ slot_src, uint64_t n,
+                                                        TriVerts* tris, TriNormals* normals) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t src = slot_src[i];
+    const double* v = verts + 9 * src;
+    const double* m = norms + 9 * src;
+    double2* tv = reinterpret_cast<double2*>(tris + i);
+    double2* tn = reinterpret_cast<double2*>(normals + i);
+    const double rank = tv[4].y, pad = tn[4].y;  // bit patterns, moved not computed
+    for (int q = 0; q < 4; ++q) {
+        tv[q] = make_double2(v[2 * q], v[2 * q + 1]);
+        tn[q] = make_double2(m[2 * q], m[2 * q + 1]);
+    }
+    tv[4] = make_double2(v[8], rank);
+    tn[4] = make_double2(m[8], pad);
+}
+
+__global__ void __launch_bounds__(kBlock) refit_level_kernel(Node* nodes, const TriVerts* tris, const int32_t* __restrict__ items,
+                                                             uint32_t count) {
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    if (t < count) refit_node(nodes, tris, items[t]);
+}
+
+__global__ void __launch_bounds__(kBlock) refit_level4_kernel(Node4* nodes4, const TriVerts* tris,
+                                                              const int32_t* __restrict__ items, uint32_t count) {
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    if (t < count) refit_node4(nodes4, tris, items[t]);
+}
+
+__global__ void refit_root_kernel(Bvh* bvh, const Node* nodes, const TriVerts* tris) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) refit_root(bvh, nodes, tris);
+}
+
+}  // namespace refit
+
+int launch_refit_validate(const double* verts, const double* norms, uint64_t n, unsigned long long* out4, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(out4, 0, sizeof(refit::Validation), st);
+    if (e != hipSuccess || n == 0) return (int)e;
+    const uint64_t blocks = (n + refit::kBlock - 1) / refit::kBlock;
+    refit::validate_kernel<<<dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(refit::kBlock), 0, st>>>(
+        verts, norms, n, reinterpret_cast<refit::Validation*>(out4));
+    return (int)hipGetLastError();
+}
+
+int launch_refit_gather(const double* verts, const double* norms, const uint32_t* slot_src, uint64_t n, TriVerts* tris,
+                        TriNormals* normals, void* stream) {
+    if (n == 0) return 0;
+    const uint64_t blocks = (n + refit::kBlock - 1) / refit::kBlock;
+    refit::gather_kernel<<<dim3((unsigned)blocks), dim3(refit::kBlock), 0, (hipStream_t)stream>>>(verts, norms, slot_src, n,
+                                                                                                   tris, normals);
+    return (int)hipGetLastError();
+}
+
+int launch_refit_levels(Node* nodes, Node4* nodes4, const TriVerts* tris, const int32_t* items, const uint32_t* host_first,
+                        uint32_t levels, void* stream) {
+    for (uint32_t l = levels; l-- > 0;) {
+        const uint32_t count = host_first[l + 1] - host_first[l];
+        if (count == 0) continue;
+        const unsigned blocks = (count + refit::kBlock - 1) / refit::kBlock;
+        if (nodes4)
+            refit::refit_level4_kernel<<<dim3(blocks), dim3(refit::kBlock), 0, (hipStream_t)stream>>>(
+                nodes4, tris, items + host_first[l], count);
+        else
+            refit::refit_level_kernel<<<dim3(blocks), dim3(refit::kBlock), 0, (hipStream_t)stream>>>(
+                nodes, tris, items + host_first[l], count);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+}
+
+int launch_refit_root(Bvh* bvh, const Node* nodes, const TriVerts* tris, void* stream) {
+    refit::refit_root_kernel<<<dim3(1), dim3(64), 0, (hipStream_t)stream>>>(bvh, nodes, tris);
+    return (int)hipGetLastError();
+}
+
+}  // namespace vr

@@ -430,3 +430,64 @@ class DeviceScene:
         out = np.zeros(len(self.spec.meshes[mesh].vertices), dtype=np.uint64)
         N.check(N.lib().vr_scene_bvh_leaf_order(self.handle, mesh, out.ctypes.data_as(C.c_void_p)))
         return out
+
+    WIDE_NODE_DTYPE = np.dtype([("bound", "<f4", (6, 4)), ("child", "<i4", (4,)), ("pad", "<i4", (4,))])
+    TRI_VERTS_DTYPE = np.dtype([("v", "<f8", (3, 3)), ("rank", "<i8")])
+    TRI_NORMALS_DTYPE = np.dtype([("n", "<f8", (3, 3)), ("pad", "<f8")])
+    BVH_ROOT_DTYPE = np.dtype([("root_box", "<f8", (6,)), ("root_box32", "<f4", (6,)), ("root", "<i4"),
+                               ("root4", "<i4"), ("pad", "<i4"), ("object", "<i4"), ("tri_base", "<i4"),
+                               ("material", "<i4")])
+    EMPTY_CHILD = -2 ** 31  # an unused slot of a 4-wide node (its six bounds are NaN)
+
+    def wide_nodes(self):
+        """The render kernel's 4-wide tree (vr_scene_wide_nodes), a structured array: bound[j][slot],
+        j = min x, max x, min y, max y, min z, max z; child >= 0 a wide node, EMPTY_CHILD, else leaf
+        holding triangle slot ~child."""
+        out = np.zeros(self.info()["wide_node_count"], dtype=self.WIDE_NODE_DTYPE)
+        if out.size:
+            N.check(N.lib().vr_scene_wide_nodes(self.handle, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def triangles(self):
+        """The triangle and normal records in slot (traversal leaf) order (vr_scene_triangles): two
+        structured arrays; `rank` is the scene-wide leaf position in the reference tree."""
+        n = self.info()["triangle_count"]
+        v = np.zeros(n, dtype=self.TRI_VERTS_DTYPE)
+        nn = np.zeros(n, dtype=self.TRI_NORMALS_DTYPE)
+        if n:
+            N.check(N.lib().vr_scene_triangles(self.handle, v.ctypes.data_as(C.c_void_p),
+                                               nn.ctypes.data_as(C.c_void_p)))
+        return v, nn
+
+    def bvh_roots(self):
+        """One record per BVH object in object order (vr_scene_bvh_roots)."""
+        n = sum(1 for o in self.spec.objects if o.kind == "bvh")
+        out = np.zeros(n, dtype=self.BVH_ROOT_DTYPE)
+        if n:
+            N.check(N.lib().vr_scene_bvh_roots(self.handle, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def update_mesh(self, mesh, vertices, normals):
+        """vr_scene_update_mesh: new vertices / normals ([n][3][3] float64, n the mesh's triangle
+        count) for mesh `mesh` of THIS device scene; both trees are refitted in place and every later
+        call behaves as on a scene created from the new geometry (bit for bit, except that exact
+        distance ties keep the creation-time ranks).  Blocks until the scene is ready.  Not
+        thread-safe against other calls on this scene; its queued asynchronous work must be done.
+
+        The owning Scene / SceneSpec are not touched: other cached DeviceScenes of the same Scene,
+        and scenes created from it later, keep the old geometry."""
+        v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1)
+        nn = np.ascontiguousarray(normals, dtype=np.float64).reshape(-1)
+        if v.size != nn.size or v.size % 9:
+            raise ValueError("vertices and normals must both be [n][3][3]")
+        N.check(N.lib().vr_scene_update_mesh(self.handle, mesh, v.size // 9, v.ctypes.data_as(C.c_void_p),
+                                             nn.ctypes.data_as(C.c_void_p)))
+
+    def update_mesh_device(self, mesh, vertices_ptr, normals_ptr, stream_ptr=None):
+        """vr_scene_update_mesh_device: as update_mesh, from device arrays of the scene's GPU (raw
+        pointers to [n][3][3] float64, n the mesh's triangle count, e.g. tensor.data_ptr()), ordered
+        after earlier work on `stream_ptr` (None: the null stream).  Blocks until the scene is ready;
+        the arrays are not read afterwards."""
+        n = len(self.spec.meshes[mesh].vertices) if 0 <= mesh < len(self.spec.meshes) else 0
+        N.check(N.lib().vr_scene_update_mesh_device(self.handle, mesh, n, C.c_void_p(vertices_ptr),
+                                                    C.c_void_p(normals_ptr), C.c_void_p(stream_ptr or 0)))
