@@ -14,11 +14,12 @@
  *   - Return value: VR_OK (0) or a negative vr_status.  The message of the last failure on the
  *     calling thread is in vr_last_error().  Nothing unwinds across the ABI; where the reference
  *     panics (singular shading basis, out-of-range tile) the call returns an error instead.
- *   - A vr_scene changes only through vr_scene_update_mesh (new vertices for one mesh, VR_HAS_SCENE_UPDATE)
- *     and the set-before-rendering hooks; between such calls it is immutable and may be shared by any
- *     number of threads.  An update is not thread-safe against any other call on the same scene, and
- *     asynchronous work of the scene still queued on any stream must have finished first (the
- *     caller's to order, as for vr_scene_set_staging_limit).
+ *   - A vr_scene changes only through vr_scene_update_mesh (new vertices for one mesh, VR_HAS_SCENE_UPDATE),
+ *     the scene edits (camera, primitives, materials, lights and a mesh's affine transform,
+ *     VR_HAS_SCENE_EDIT) and the set-before-rendering hooks; between such calls it is immutable and may
+ *     be shared by any number of threads.  An update or edit is not thread-safe against any other
+ *     call on the same scene, and asynchronous work of the scene still queued on any stream must
+ *     have finished first (the caller's to order, as for vr_scene_set_staging_limit).
  *     Render calls are re-entrant.  Each call holds its own stream, staging buffer, work-queue
  *     counter and device error word for its duration (a per-scene pool of call contexts), so
  *     concurrent calls neither serialise on shared scratch nor see each other's errors
@@ -265,6 +266,84 @@ int vr_scene_update_mesh_device(vr_scene* scene, uint32_t mesh, uint64_t triangl
 int vr_scene_wide_nodes(const vr_scene* scene, void* out);
 int vr_scene_triangles(const vr_scene* scene, void* out_verts, void* out_normals);
 int vr_scene_bvh_roots(const vr_scene* scene, void* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Scene edits: everything else a caller moves between frames -- the camera, the plane and the
+ * spheres, a material, the Whitted lights -- and a mesh placed by an affine matrix, without
+ * vr_scene_destroy + vr_scene_create.  Added under ABI 10 (VR_HAS_SCENE_EDIT).
+ *
+ * For every call below, as for vr_scene_update_mesh:
+ * The call blocks: when it returns VR_OK the scene is ready and the arguments may be freed.
+ * It is not thread-safe against any other call on the scene, and the scene's queued asynchronous work
+ *   must have finished first.
+ * Errors come before anything is modified: a failed call leaves the scene bit for bit as it was.
+ * Afterwards every entry point (renders, films, samples, traces, queries, integrate, camera rays, the
+ *   block cull, vr_scene_get_info) answers as on a scene created from the edited description with the
+ *   same flags, bit for bit.  Topology, ranks, node counts, stack depths, the pass counter, the staging
+ *   limit, the debug hooks, the pooled call contexts and the scene's device allocation stay.
+ * On a VR_SCENE_HOST_ONLY scene each call changes the host records only, with no device call.
+ * --------------------------------------------------------------------------------------------- */
+#define VR_HAS_SCENE_EDIT 1
+/* vr_scene_desc::camera_location.  A coordinate that is not finite: VR_ERROR_INVALID_ARGUMENT.
+ * vr_scene_info::extent and the cull margins follow.  The camera is a launch argument, not in HBM:
+ * this call makes no device call at all, on any scene. */
+int vr_scene_set_camera(vr_scene* scene, vr_vec3 location);
+/* Entries first .. first + count - 1 of vr_scene_desc::primitives; kind, material, vector and scalar may
+ * all change.  Every row a primitive list made from such an entry is rebuilt as vr_scene_create builds it
+ * (an entry in several overlapping lists has several rows, one in none has none); extent follows.
+ * VR_ERROR_INVALID_ARGUMENT: a range past primitive_count, a null array with count > 0, an unknown
+ * kind, a material index >= the creation desc's material_count.  count == 0 is VR_OK. */
+int vr_scene_update_primitives(vr_scene* scene, uint32_t first, uint32_t count, const vr_primitive_desc* primitives);
+/* Material `index` of vr_scene_desc::materials, validated as at creation (kind, 1..64 samples, non-null
+ * samples).  VR_SCENE_INFO_NAN_FREE, the early stop and the kernel choice follow the new set of
+ * materials as on a fresh scene (a Phong or dielectric material clears NAN_FREE). */
+int vr_scene_update_material(vr_scene* scene, uint32_t index, const vr_material_desc* material);
+/* The Whitted integrator's ambient spectrum, light spectra and directions (stored as given).  kind and
+ * light_count must equal the scene's, else VR_ERROR_INVALID_ARGUMENT; spectra are validated as at
+ * creation.  NULL means SimpleRandomIntegrator, which must then be the scene's: on such a scene the call
+ * validates and changes nothing. */
+int vr_scene_set_lights(vr_scene* scene, const vr_integrator_desc* integrator);
+/* Mesh `mesh` becomes the affine image of its BASE geometry: the vertices and normals given at creation
+ * or by the latest successful vr_scene_update_mesh[_device].  Transforms do not compound: a turntable
+ * passes the absolute pose each frame and never drifts.  matrix: row-major 3 x 4, m = [A | t].  In f64,
+ * without contraction, in exactly this order:
+ *   vertex component c:  ((m[4c] * x + m[4c + 1] * y) + m[4c + 2] * z) + m[4c + 3]
+ *   normal component c:  (K[c][0] * nx + K[c][1] * ny) + K[c][2] * nz
+ *   K, the cofactor matrix of A, once per call: K[i][j] = A[i+1][j+1] * A[i+2][j+2] - A[i+1][j+2] * A[i+2][j+1],
+ *   indices mod 3 -- the exact rule (A a) x (A b) = K (a x b), so shading normals stay on their
+ *   triangle's side for any A, reflections included.  Normals are not normalised (the reference
+ *   normalises the interpolated normal at the hit).
+ * The identity matrix reproduces the base, except that -0.0 coordinates become +0.0 (x + 0.0).
+ * Then both trees are refitted as by vr_scene_update_mesh, whose description applies, the tie caveat
+ *   included: exact distance ties between two triangles of the mesh keep the creation-time ranks where
+ *   a fresh scene would re-rank.  The `primitive` a hit on the mesh reports (vr_hit_record, vr_ray_hit) is
+ *   that creation-time leaf position too; vr_scene_bvh_leaf_order maps it to the input triangle, which is
+ *   the one a fresh scene hits.
+ * The base is a copy of the mesh's triangle and normal records, 160 B per triangle, allocated at the
+ *   mesh's first transform and added to vr_scene_info::device_bytes (beside the update plan); it follows
+ *   every later vr_scene_update_mesh.  On the device the call reads only resident records: nothing
+ *   per triangle is uploaded.
+ * stream: the call is ordered after earlier work on it (NULL = the null stream), as
+ *   vr_scene_update_mesh_device; ignored on VR_SCENE_HOST_ONLY scenes.
+ * VR_ERROR_INVALID_ARGUMENT: a null scene or matrix, a bad mesh index, a matrix entry that is not finite.
+ * VR_ERROR_UNSUPPORTED: a transformed vertex coordinate that is not finite (overflow); the scene and the
+ *   base stay as they were.  A singular A is allowed: its degenerate triangles clear NAN_FREE, as the
+ *   same arrays through vr_scene_update_mesh would.  An empty mesh: VR_OK after the matrix check.  A mesh
+ *   that backs no object is transformed like any other. */
+int vr_scene_transform_mesh(vr_scene* scene, uint32_t mesh, const double matrix[12], void* stream);
+/* Inspection of what the edits change (always the current state; device scenes read back).  *count
+ * receives the number of records; out == NULL returns only the count.
+ * vr_scene_primitives: one 128-B record per primitive of every primitive list, in kernel order (object
+ *   order, then list position) = { int32 kind, material, object, position; double vec[3] (plane normal /
+ *   sphere centre), tan[3], cot[3] (plane basis), scalar (plane distance / sphere radius), pre[3] (plane:
+ *   normal * distance; sphere: centre^2 per component), scalar2 (sphere: radius^2) }.
+ * vr_scene_materials: one 1,080-B record per material row: the desc's materials, then for a Whitted scene
+ *   the ambient row and one row per light, then the sky's lookup row = { int32 kind, n (samples);
+ *   double shortest, longest, diffuse, reflection, smoothness, samples[64], knots[64] (the sample
+ *   wavelengths), inv_step }. */
+int vr_scene_primitives(const vr_scene* scene, void* out, uint32_t* count);
+int vr_scene_materials(const vr_scene* scene, void* out, uint32_t* count);
+int vr_scene_get_camera(const vr_scene* scene, vr_vec3* out);
 
 /* util::Tile (src/util/tile_iterator.rs:1-7): half-open row/column ranges of the full image. */
 typedef struct vr_tile {

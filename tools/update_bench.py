@@ -1,6 +1,7 @@
-"""What vr_scene_update_mesh costs against vr_scene_create, and how far a refitted tree degrades.
+"""What vr_scene_update_mesh and the scene edits cost against vr_scene_create, and how far a refitted
+tree degrades.
 
-    python tools/update_bench.py [--meshes bunny,c5] [--updates 20] [--out-dir profiles/r09/update]
+    python tools/update_bench.py [--meshes bunny,c5] [--updates 20] [--out-dir profiles/r10/edit]
 
 Per mesh (the stand-in bunny, 69,312 triangles, and C5's 1,051,392-triangle mesh, each in main.rs's
 scene of a plane and spheres), one JSON under --out-dir:
@@ -13,7 +14,13 @@ scene of a plane and spheres), one JSON under --out-dir:
   degradation    the render kernel's time for one 1024 x 1024 frame at 16 spp on the refitted tree and on
                  a freshly built tree of the same geometry, for no deformation, per-vertex noise of 1 % of
                  the mesh radius, and a twist of pi about the vertical axis -- with a check that both
-                 render the same records.
+                 render the same records;
+  edits          the scene edits, in the same run: the mesh's first vr_scene_transform_mesh (base snapshot
+                 included) and base_bytes, what it adds to device_bytes; median and best wall time of
+                 --updates steady-state transforms (a rotation about the vertical axis through the mesh's
+                 centre, a new absolute angle each time), to be read beside `device` above -- the
+                 transform runs the update's launches plus two passes over resident records; and the
+                 wall time of set_camera, update_primitives (3 spheres) and update_material.
 Nothing here is asserted by the test suite; the comparison that matters is update against creation in
 the same run.  Wall times are host clocks around blocking calls.
 """
@@ -145,6 +152,40 @@ def run(name, updates):
             "ratio": round(refit_ms / fresh_ms, 4),
             "records_equal": bool(torch.equal(refit_state.view(torch.int64), fresh_state.view(torch.int64)))}
         fresh.release()
+    out["edits"] = edits(ds, v, n, updates)
+    return out
+
+
+def edits(ds, v, n, updates):
+    """The scene edits on the resident scene `ds` (main.rs's scene: a plane, three spheres, the mesh)."""
+    ds.update_mesh(0, v, n)  # the base: the undeformed mesh
+    flat = v.reshape(-1, 3)
+    cx, _, cz = 0.5 * (flat.min(axis=0) + flat.max(axis=0))
+
+    def turn(k):  # rotate by angle k / 10 about the vertical axis through the mesh's centre
+        c, s = np.cos(0.1 * k), np.sin(0.1 * k)
+        return [c, 0.0, s, cx - (c * cx + s * cz), 0.0, 1.0, 0.0, 0.0, -s, 0.0, c, cz - (-s * cx + c * cz)]
+
+    def median_of(fn):
+        fn(0)
+        t = [timed(lambda: fn(k))[1] for k in range(1, updates + 1)]
+        return {"ms_median": round(statistics.median(t), 4), "ms_min": round(min(t), 4), "calls": updates}
+
+    out = {}
+    before = ds.info()["device_bytes"]
+    _, out["first_transform_ms"] = timed(lambda: ds.transform_mesh(0, turn(1)))
+    out["base_bytes"] = ds.info()["device_bytes"] - before
+    out["transform"] = median_of(lambda k: ds.transform_mesh(0, turn(k)))
+    cam = np.array(ds.camera())
+    out["set_camera"] = median_of(lambda k: ds.set_camera(cam + [0.01 * k, 0.0, 0.0]))
+    spheres = [p for p in ds.spec.objects[0].primitives if p.kind == 1][:3]
+    first = ds.spec.objects[0].primitives.index(spheres[0])
+    out["update_primitives_3_spheres"] = median_of(lambda k: ds.update_primitives(first, [
+        type(p)(p.kind, p.material, (p.vector[0], p.vector[1] + 0.01 * k, p.vector[2]), p.scalar) for p in spheres]))
+    mat = ds.spec.materials[ds.spec.meshes[0].material]
+    out["update_material"] = median_of(lambda k: ds.update_material(
+        ds.spec.meshes[0].material, type(mat)(mat.kind, mat.colour, 0.05 + 0.001 * k, mat.reflection_strength,
+                                              mat.smoothness)))
     return out
 
 
@@ -152,7 +193,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--meshes", default="bunny,c5")
     ap.add_argument("--updates", type=int, default=20)
-    ap.add_argument("--out-dir", default=os.path.join("profiles", "r09", "update"))
+    ap.add_argument("--out-dir", default=os.path.join("profiles", "r10", "edit"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("update_bench needs a GPU: no timing is taken without one")

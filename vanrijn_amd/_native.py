@@ -174,6 +174,14 @@ SIGNATURES = {
     "vr_scene_wide_nodes": (C.c_int, [_p, _p]),
     "vr_scene_triangles": (C.c_int, [_p, _p, _p]),
     "vr_scene_bvh_roots": (C.c_int, [_p, _p]),
+    "vr_scene_set_camera": (C.c_int, [_p, Vec3]),
+    "vr_scene_update_primitives": (C.c_int, [_p, _u32, _u32, C.POINTER(PrimitiveDesc)]),
+    "vr_scene_update_material": (C.c_int, [_p, _u32, C.POINTER(MaterialDesc)]),
+    "vr_scene_set_lights": (C.c_int, [_p, C.POINTER(IntegratorDesc)]),
+    "vr_scene_transform_mesh": (C.c_int, [_p, _u32, _p, _p]),
+    "vr_scene_primitives": (C.c_int, [_p, _p, C.POINTER(C.c_uint32)]),
+    "vr_scene_materials": (C.c_int, [_p, _p, C.POINTER(C.c_uint32)]),
+    "vr_scene_get_camera": (C.c_int, [_p, C.POINTER(Vec3)]),
     "vr_partial_render_scene": (C.c_int, [_p, TileC, _u64, _u64, C.POINTER(AccumulationBufferC)]),
     "vr_render_tile": (C.c_int, [_p, C.POINTER(RenderParams), C.POINTER(AccumulationBufferC)]),
     "vr_render_tile_device": (C.c_int, [_p, C.POINTER(RenderParams), _p, _p, _u32, C.POINTER(LaunchStats)]),

@@ -615,6 +615,21 @@ struct vr_scene {
         size_t stage_bytes = 0;
     };
     std::vector<UpdatePlan> plans;
+    // scene edits (vr_scene_set_camera, vr_scene_update_primitives, vr_scene_update_material,
+    // vr_scene_set_lights): what of the creation desc they need
+    uint32_t desc_materials = 0;                   // vr_scene_desc::material_count (the addressable rows)
+    std::vector<std::vector<uint32_t>> prim_rows;  // per vr_scene_desc::primitives entry: its rows in prims
+    // vr_scene_transform_mesh: a mesh's base geometry, a copy of its triangle and normal records in slot
+    // order (host vectors on VR_SCENE_HOST_ONLY scenes, else d_base = [n TriVerts | n TriNormals]), made
+    // at the first transform; a successful vr_scene_update_mesh marks it stale, and the next transform
+    // takes it again from the records
+    struct MeshBase {
+        bool current = false;
+        std::vector<vr::TriVerts> tris;
+        std::vector<vr::TriNormals> normals;
+        void* d_base = nullptr;
+    };
+    std::vector<MeshBase> bases;
 };
 
 // The render kernel addresses the triangle and 4-wide node arrays with 32-bit byte offsets from
@@ -816,6 +831,77 @@ static void fill_knots(vr::Material& m) {
     m.inv_step = m.n > 1 && range > 0.0 ? (double)(m.n - 1) / range : 0.0;
 }
 
+// The rows of the scene block that vr_scene_create and the scene edits both make: one definition
+// each, so an edited scene holds a fresh scene's bits.  Each returns a message on a bad description.
+static const char* spectrum_row(const vr_spectrum& sp, vr::Material& dm) {
+    if (sp.sample_count < 1 || sp.sample_count > VR_MAX_SPECTRUM_SAMPLES || !sp.samples)
+        return "spectrum needs 1..64 samples";
+    dm = vr::Material{};
+    dm.n = (int32_t)sp.sample_count;
+    dm.shortest = sp.shortest_wavelength;
+    dm.longest = sp.longest_wavelength;
+    std::memcpy(dm.samples, sp.samples, sizeof(double) * sp.sample_count);
+    fill_knots(dm);
+    return nullptr;
+}
+
+static const char* material_row(const vr_material_desc& m, vr::Material& dm) {
+    if (m.kind < VR_MATERIAL_LAMBERTIAN || m.kind > VR_MATERIAL_DIELECTRIC) return "unknown material kind";
+    if (spectrum_row(m.colour, dm)) return "material spectrum needs 1..64 samples";
+    dm.kind = m.kind;
+    dm.diffuse = m.diffuse_strength;
+    dm.reflection = m.reflection_strength;
+    dm.smoothness = m.smoothness;
+    return nullptr;
+}
+
+// the Whitted rows: ambient, then one per light; dirs: 3 per light, stored as given
+static const char* light_rows(const vr_integrator_desc& ig, std::vector<vr::Material>& rows, std::vector<double>& dirs) {
+    if (ig.light_count > VR_MAX_LIGHTS || (ig.light_count && !ig.lights)) return "bad light list";
+    vr::Material dm;
+    if (spectrum_row(ig.ambient_light, dm)) return "ambient light spectrum needs 1..64 samples";
+    rows.push_back(dm);
+    for (uint32_t j = 0; j < ig.light_count; ++j) {
+        if (spectrum_row(ig.lights[j].spectrum, dm)) return "light spectrum needs 1..64 samples";
+        rows.push_back(dm);
+        const vr_vec3& d = ig.lights[j].direction;
+        dirs.insert(dirs.end(), {d.x, d.y, d.z});
+    }
+    return nullptr;
+}
+
+// entry `p` of vr_scene_desc::primitives as the row at `position` of the list of scene object `object`
+static const char* prim_row(const vr_primitive_desc& p, int32_t object, int32_t position, vr::Prim& dp) {
+    dp = vr::Prim{};
+    dp.kind = p.kind;
+    dp.material = (int32_t)p.material;
+    dp.object = object;
+    dp.position = position;
+    dp.scalar = p.scalar;
+    if (p.kind == VR_PRIMITIVE_PLANE) {
+        // Plane::new (plane.rs:18-31)
+        H3 n = hnormalize({p.vector.x, p.vector.y, p.vector.z});
+        double ax = std::fabs(n.x), ay = std::fabs(n.y), az = std::fabs(n.z);
+        int k2 = ax < ay ? (ax < az ? 0 : 2) : (ay < az ? 1 : 2);  // smallest_coord
+        H3 axis{k2 == 0 ? 1.0 : 0.0, k2 == 1 ? 1.0 : 0.0, k2 == 2 ? 1.0 : 0.0};
+        H3 cot = hnormalize(hcross(n, axis));
+        H3 tan = hcross(n, cot);
+        dp.vec[0] = n.x; dp.vec[1] = n.y; dp.vec[2] = n.z;
+        dp.tan[0] = tan.x; dp.tan[1] = tan.y; dp.tan[2] = tan.z;
+        dp.cot[0] = cot.x; dp.cot[1] = cot.y; dp.cot[2] = cot.z;
+        dp.pre[0] = n.x * p.scalar; dp.pre[1] = n.y * p.scalar; dp.pre[2] = n.z * p.scalar;
+    } else if (p.kind == VR_PRIMITIVE_SPHERE) {
+        dp.vec[0] = p.vector.x; dp.vec[1] = p.vector.y; dp.vec[2] = p.vector.z;
+        dp.pre[0] = p.vector.x * p.vector.x;
+        dp.pre[1] = p.vector.y * p.vector.y;
+        dp.pre[2] = p.vector.z * p.vector.z;
+        dp.scalar2 = p.scalar * p.scalar;
+    } else {
+        return "unknown primitive kind";
+    }
+    return nullptr;
+}
+
 namespace {
 
 int stack_depth(const vr_scene* s) { return std::max(1, s->max_depth - 1); }  // binary tree walks
@@ -823,6 +909,35 @@ int wide_stack_depth(const vr_scene* s) { return s->wide_stack + 1; }  // render
 
 // The scene scalars that depend on mesh geometry, from their per-mesh parts: at creation, and again
 // after vr_scene_update_mesh replaced one mesh's part -- so an updated scene holds a fresh scene's values.
+// base_extent: the camera's and every primitive row's share of the extent (a row keeps the entry's
+// scalar, and a sphere's centre, as given)
+void update_base_extent(vr_scene* s) {
+    double extent = std::max({std::fabs(s->camera[0]), std::fabs(s->camera[1]), std::fabs(s->camera[2])});
+    for (const vr::Prim& p : s->prims) {
+        if (p.kind == VR_PRIMITIVE_PLANE)
+            extent = std::max(extent, std::fabs(p.scalar));
+        else
+            extent = std::max({extent, std::fabs(p.vec[0]) + std::fabs(p.scalar), std::fabs(p.vec[1]) + std::fabs(p.scalar),
+                               std::fabs(p.vec[2]) + std::fabs(p.scalar)});
+    }
+    s->base_extent = extent;
+}
+
+// mats and dark0's materials-only part, over the desc's materials (not the light and sky rows)
+void update_material_scalars(vr_scene* s) {
+    s->mats = 0;
+    s->dark0_materials = true;
+    for (uint32_t i = 0; i < s->desc_materials; ++i) {
+        const vr::Material& m = s->materials[i];
+        const vr_spectrum colour{m.shortest, m.longest, (uint32_t)m.n, m.samples};
+        if (vr_spectrum_intensity_at_wavelength(&colour, 0.0) != 0.0) s->dark0_materials = false;
+        s->mats |= m.kind == VR_MATERIAL_LAMBERTIAN ? 1 : (m.kind == VR_MATERIAL_REFLECTIVE ? 2 : 4);
+        // the dielectric's strength at 0 nm is not its eta(0): a path cut at the recursion limit
+        // (lambda 0) needs the general lambda-0 chain
+        if (m.kind == VR_MATERIAL_DIELECTRIC) s->dark0_materials = false;
+    }
+}
+
 void update_scalars(vr_scene* s) {
     double extent = s->base_extent;
     for (double e : s->mesh_extent) extent = std::max(extent, e);
@@ -1421,60 +1536,25 @@ int vr_scene_create(const vr_scene_desc* desc, int32_t device, uint32_t flags, v
     s->camera[0] = desc->camera_location.x;
     s->camera[1] = desc->camera_location.y;
     s->camera[2] = desc->camera_location.z;
-    double extent = std::max({std::fabs(s->camera[0]), std::fabs(s->camera[1]), std::fabs(s->camera[2])});
     auto bad = [&](const std::string& m) {
         delete s;
         return fail(VR_ERROR_INVALID_ARGUMENT, m);
     };
 
     for (uint32_t i = 0; i < desc->material_count; ++i) {
-        const vr_material_desc& m = desc->materials[i];
-        if (m.kind < VR_MATERIAL_LAMBERTIAN || m.kind > VR_MATERIAL_DIELECTRIC) return bad("unknown material kind");
-        if (m.colour.sample_count < 1 || m.colour.sample_count > VR_MAX_SPECTRUM_SAMPLES || !m.colour.samples)
-            return bad("material spectrum needs 1..64 samples");
-        vr::Material dm{};
-        dm.kind = m.kind;
-        dm.n = (int32_t)m.colour.sample_count;
-        dm.shortest = m.colour.shortest_wavelength;
-        dm.longest = m.colour.longest_wavelength;
-        dm.diffuse = m.diffuse_strength;
-        dm.reflection = m.reflection_strength;
-        dm.smoothness = m.smoothness;
-        std::memcpy(dm.samples, m.colour.samples, sizeof(double) * m.colour.sample_count);
-        fill_knots(dm);
+        vr::Material dm;
+        if (const char* why = material_row(desc->materials[i], dm)) return bad(why);
         s->materials.push_back(dm);
-        if (vr_spectrum_intensity_at_wavelength(&m.colour, 0.0) != 0.0) s->dark0 = false;
-        s->mats |= m.kind == VR_MATERIAL_LAMBERTIAN ? 1 : (m.kind == VR_MATERIAL_REFLECTIVE ? 2 : 4);
-        // the dielectric's strength at 0 nm is not its eta(0): a path cut at the recursion limit
-        // (lambda 0) needs the general lambda-0 chain
-        if (m.kind == VR_MATERIAL_DIELECTRIC) s->dark0 = false;
     }
+    s->desc_materials = desc->material_count;
+    update_material_scalars(s);
     // integrator: Whitted's ambient and light spectra become extra material rows
     if (desc->integrator && desc->integrator->kind == VR_INTEGRATOR_WHITTED) {
         const vr_integrator_desc& ig = *desc->integrator;
-        if (ig.light_count > VR_MAX_LIGHTS || (ig.light_count && !ig.lights)) return bad("bad light list");
-        auto spectrum_row = [&](const vr_spectrum& sp, vr::Material& dm) {
-            if (sp.sample_count < 1 || sp.sample_count > VR_MAX_SPECTRUM_SAMPLES || !sp.samples) return false;
-            dm = vr::Material{};
-            dm.n = (int32_t)sp.sample_count;
-            dm.shortest = sp.shortest_wavelength;
-            dm.longest = sp.longest_wavelength;
-            std::memcpy(dm.samples, sp.samples, sizeof(double) * sp.sample_count);
-            fill_knots(dm);
-            return true;
-        };
         s->dev.integrator = VR_INTEGRATOR_WHITTED;
         s->dev.light_base = (int32_t)s->materials.size();
         s->dev.light_count = (int32_t)ig.light_count;
-        vr::Material dm;
-        if (!spectrum_row(ig.ambient_light, dm)) return bad("ambient light spectrum needs 1..64 samples");
-        s->materials.push_back(dm);
-        for (uint32_t j = 0; j < ig.light_count; ++j) {
-            if (!spectrum_row(ig.lights[j].spectrum, dm)) return bad("light spectrum needs 1..64 samples");
-            s->materials.push_back(dm);
-            const vr_vec3& d = ig.lights[j].direction;
-            s->light_dirs.insert(s->light_dirs.end(), {d.x, d.y, d.z});
-        }
+        if (const char* why = light_rows(ig, s->materials, s->light_dirs)) return bad(why);
     } else if (desc->integrator && desc->integrator->kind != VR_INTEGRATOR_SIMPLE_RANDOM) {
         return bad("unknown integrator kind");
     }
@@ -1489,6 +1569,7 @@ int vr_scene_create(const vr_scene_desc* desc, int32_t device, uint32_t flags, v
     }
     // objects: primitive lists keep their order; BVHs are built per mesh
     std::vector<int> mesh_object(desc->mesh_count, -1);
+    s->prim_rows.resize(desc->primitive_count);
     for (uint32_t oi = 0; oi < desc->object_count; ++oi) {
         const vr_object_desc& o = desc->objects[oi];
         if (o.kind == VR_OBJECT_PRIMITIVE_LIST) {
@@ -1496,37 +1577,9 @@ int vr_scene_create(const vr_scene_desc* desc, int32_t device, uint32_t flags, v
             for (uint32_t k = 0; k < o.count; ++k) {
                 const vr_primitive_desc& p = desc->primitives[o.first + k];
                 if (p.material >= desc->material_count) return bad("primitive material out of range");
-                vr::Prim dp{};
-                dp.kind = p.kind;
-                dp.material = (int32_t)p.material;
-                dp.object = (int32_t)oi;
-                dp.position = (int32_t)k;
-                dp.scalar = p.scalar;
-                if (p.kind == VR_PRIMITIVE_PLANE) {
-                    // Plane::new (plane.rs:18-31)
-                    H3 n = hnormalize({p.vector.x, p.vector.y, p.vector.z});
-                    double ax = std::fabs(n.x), ay = std::fabs(n.y), az = std::fabs(n.z);
-                    int k2 = ax < ay ? (ax < az ? 0 : 2) : (ay < az ? 1 : 2);  // smallest_coord
-                    H3 axis{k2 == 0 ? 1.0 : 0.0, k2 == 1 ? 1.0 : 0.0, k2 == 2 ? 1.0 : 0.0};
-                    H3 cot = hnormalize(hcross(n, axis));
-                    H3 tan = hcross(n, cot);
-                    dp.vec[0] = n.x; dp.vec[1] = n.y; dp.vec[2] = n.z;
-                    dp.tan[0] = tan.x; dp.tan[1] = tan.y; dp.tan[2] = tan.z;
-                    dp.cot[0] = cot.x; dp.cot[1] = cot.y; dp.cot[2] = cot.z;
-                    dp.pre[0] = n.x * p.scalar; dp.pre[1] = n.y * p.scalar; dp.pre[2] = n.z * p.scalar;
-                    extent = std::max(extent, std::fabs(p.scalar));
-                } else if (p.kind == VR_PRIMITIVE_SPHERE) {
-                    dp.vec[0] = p.vector.x; dp.vec[1] = p.vector.y; dp.vec[2] = p.vector.z;
-                    dp.pre[0] = p.vector.x * p.vector.x;
-                    dp.pre[1] = p.vector.y * p.vector.y;
-                    dp.pre[2] = p.vector.z * p.vector.z;
-                    dp.scalar2 = p.scalar * p.scalar;
-                    extent = std::max({extent, std::fabs(p.vector.x) + std::fabs(p.scalar),
-                                       std::fabs(p.vector.y) + std::fabs(p.scalar),
-                                       std::fabs(p.vector.z) + std::fabs(p.scalar)});
-                } else {
-                    return bad("unknown primitive kind");
-                }
+                vr::Prim dp;
+                if (const char* why = prim_row(p, (int32_t)oi, (int32_t)k, dp)) return bad(why);
+                s->prim_rows[o.first + k].push_back((uint32_t)s->prims.size());
                 s->prims.push_back(dp);
             }
         } else if (o.kind == VR_OBJECT_BVH) {
@@ -1546,14 +1599,14 @@ int vr_scene_create(const vr_scene_desc* desc, int32_t device, uint32_t flags, v
         if (mesh_object[mi] >= 0 && m.triangle_count && m.vertices && m.normals && !shading_finite(m))
             s->mesh_finite[mi] = 0;
     }
-    s->dark0_materials = s->dark0;
-    s->base_extent = extent;
+    update_base_extent(s);
     s->mesh_extent.assign(desc->mesh_count, 0.0);
     s->mesh_object = mesh_object;
     s->mesh_bvh.assign(desc->mesh_count, -1);
     s->mesh_node_base.assign(desc->mesh_count, 0);
     s->mesh_root4.assign(desc->mesh_count, vr::kEmptyChild);
     s->plans.resize(desc->mesh_count);
+    s->bases.resize(desc->mesh_count);
     s->leaf_order.resize(desc->mesh_count);
     s->mesh_tri_base.assign(desc->mesh_count, 0);
     // device build: requested, a device exists for it, and no NaN coordinate (the reference's
@@ -1722,6 +1775,8 @@ void vr_scene_destroy(vr_scene* s) {
             if (p.d_plan) (void)hipFree(p.d_plan);
             if (p.d_stage) (void)hipFree(p.d_stage);
         }
+        for (auto& b : s->bases)
+            if (b.d_base) (void)hipFree(b.d_base);
         if (s->d_block) (void)hipFree(s->d_block);
     }
     for (auto& kv : s->deferred)
@@ -1900,6 +1955,8 @@ int build_update_plan(vr_scene* s, uint32_t mi) {
     return VR_OK;
 }
 
+void refit_host(vr_scene* s, uint32_t mi, double max_abs, const vr::refit::Validation& val);
+
 // the refit in plain C++ on the host arrays (VR_SCENE_HOST_ONLY): the steps of vr_refit.hip in its order
 int update_mesh_host(vr_scene* s, uint32_t mi, uint64_t n, const double* verts, const double* norms) {
     vr::refit::Validation val{};
@@ -1922,6 +1979,14 @@ int update_mesh_host(vr_scene* s, uint32_t mi, uint64_t n, const double* verts, 
         std::memcpy(s->tris[tri_base + i].v, verts + 9 * (uint64_t)p.slot_src[i], 9 * sizeof(double));
         std::memcpy(s->normals[tri_base + i].n, norms + 9 * (uint64_t)p.slot_src[i], 9 * sizeof(double));
     }
+    s->bases[mi].current = false;
+    refit_host(s, mi, max_abs, val);
+    return VR_OK;
+}
+
+// both trees, the root record and the scene scalars once the mesh's records hold the new geometry
+void refit_host(vr_scene* s, uint32_t mi, double max_abs, const vr::refit::Validation& val) {
+    const vr_scene::UpdatePlan& p = s->plans[mi];
     for (size_t l = p.first2.size() - 1; l-- > 0;)
         for (uint32_t k = p.first2[l]; k < p.first2[l + 1]; ++k)
             vr::refit::refit_node(s->nodes.data(), s->tris.data(), p.items2[k]);
@@ -1932,8 +1997,9 @@ int update_mesh_host(vr_scene* s, uint32_t mi, uint64_t n, const double* verts, 
     s->mesh_extent[mi] = max_abs;
     s->mesh_finite[mi] = s->mesh_object[mi] < 0 || val.not_finite == 0;
     update_scalars(s);
-    return VR_OK;
 }
+
+int refit_device(vr_scene* s, uint32_t mi, const vr::refit::Validation& val, hipStream_t st);
 
 // ... and on the device; `device_arrays`: verts / norms are device pointers, else they are uploaded first
 int update_mesh_device(vr_scene* s, uint32_t mi, uint64_t n, const double* verts, const double* norms,
@@ -1971,12 +2037,24 @@ int update_mesh_device(vr_scene* s, uint32_t mi, uint64_t n, const double* verts
     VR_HIP(hipStreamSynchronize(st));
     if (val.nonfinite) return fail(VR_ERROR_UNSUPPORTED, "scene update: a vertex coordinate is not finite");
     const int32_t tri_base = s->mesh_tri_base[mi];
-    vr::TriVerts* tris = const_cast<vr::TriVerts*>(s->dev.tris);
-    vr::Node* nodes = const_cast<vr::Node*>(s->dev.nodes);
-    e = vr::launch_refit_gather(verts, norms, p.d_slot_src, n, tris + tri_base,
+    e = vr::launch_refit_gather(verts, norms, p.d_slot_src, n, const_cast<vr::TriVerts*>(s->dev.tris) + tri_base,
                                 const_cast<vr::TriNormals*>(s->dev.normals) + tri_base, st);
     if (e) return dev(e, "scene update (gather)");
-    e = vr::launch_refit_levels(nodes, nullptr, tris, p.d_items2, p.first2.data(), (uint32_t)p.first2.size() - 1, st);
+    const int rc = refit_device(s, mi, val, st);
+    if (rc == VR_OK) s->bases[mi].current = false;
+    return rc;
+}
+
+// both trees, the root record and the scene scalars once the launches that write the mesh's records are
+// queued on `st`; blocks until the scene is ready
+int refit_device(vr_scene* s, uint32_t mi, const vr::refit::Validation& val, hipStream_t st) {
+    const vr_scene::UpdatePlan& p = s->plans[mi];
+    auto dev = [](int e, const char* what) {
+        return fail(VR_ERROR_DEVICE, std::string(what) + ": " + hipGetErrorString((hipError_t)e));
+    };
+    vr::TriVerts* tris = const_cast<vr::TriVerts*>(s->dev.tris);
+    vr::Node* nodes = const_cast<vr::Node*>(s->dev.nodes);
+    int e = vr::launch_refit_levels(nodes, nullptr, tris, p.d_items2, p.first2.data(), (uint32_t)p.first2.size() - 1, st);
     if (e) return dev(e, "scene update (binary refit)");
     if (!p.items4.empty()) {
         e = vr::launch_refit_levels(nullptr, const_cast<vr::Node4*>(s->dev.nodes4), tris, p.d_items4, p.first4.data(),
@@ -2023,6 +2101,210 @@ int vr_scene_update_mesh(vr_scene* s, uint32_t mesh, uint64_t triangle_count, co
 int vr_scene_update_mesh_device(vr_scene* s, uint32_t mesh, uint64_t triangle_count, const double* vertices,
                                 const double* normals, void* stream) {
     return update_mesh_checked(s, mesh, triangle_count, vertices, normals, true, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// Scene edits: camera, primitives, materials, lights, and a mesh's affine transform from its
+// resident base geometry.  Each validates first, then changes the host records and copies the
+// changed rows into the scene block (VR_SCENE_HOST_ONLY: host records only, no device call).
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// rows `first` .. of a device array of the scene block <- the host records (a host-only scene has no block)
+int copy_rows(const vr_scene* s, const void* device_array, size_t row_bytes, size_t first, const void* src,
+              size_t count) {
+    if (s->host_only || count == 0) return VR_OK;
+    VR_HIP(hipSetDevice(s->device));
+    char* dst = (char*)const_cast<void*>(device_array) + first * row_bytes;
+    VR_HIP(hipMemcpy(dst, src, count * row_bytes, hipMemcpyHostToDevice));
+    return VR_OK;
+}
+
+// rows of the scene block for an inspector: the host records, or read back on device scenes
+int dump_rows(const vr_scene* s, const void* device_src, const void* host_src, size_t bytes, void* out) {
+    if (bytes == 0) return VR_OK;
+    if (s->host_only) {
+        std::memcpy(out, host_src, bytes);
+        return VR_OK;
+    }
+    VR_HIP(hipSetDevice(s->device));
+    VR_HIP(hipMemcpy(out, device_src, bytes, hipMemcpyDeviceToHost));
+    return VR_OK;
+}
+
+// [A | t] and the cofactor matrix of A: K[i][j] = A[i+1][j+1] * A[i+2][j+2] - A[i+1][j+2] * A[i+2][j+1],
+// indices mod 3, so that (A a) x (A b) = K (a x b)
+vr::refit::Affine affine_of(const double m[12]) {
+    vr::refit::Affine a;
+    std::memcpy(a.m, m, sizeof a.m);
+    auto A = [&](int i, int j) { return m[4 * (i % 3) + (j % 3)]; };
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) a.k[3 * i + j] = A(i + 1, j + 1) * A(i + 2, j + 2) - A(i + 1, j + 2) * A(i + 2, j + 1);
+    return a;
+}
+
+const char* kOverflow = "scene transform: a transformed vertex coordinate is not finite";
+
+int transform_mesh_host(vr_scene* s, uint32_t mi, uint64_t n, const vr::refit::Affine& a) {
+    vr_scene::MeshBase& b = s->bases[mi];
+    const int32_t tri_base = s->mesh_tri_base[mi];
+    if (!b.current) {
+        b.tris.assign(s->tris.begin() + tri_base, s->tris.begin() + tri_base + n);
+        b.normals.assign(s->normals.begin() + tri_base, s->normals.begin() + tri_base + n);
+        b.current = true;
+    }
+    vr::refit::Validation val{};
+    double max_abs = 0.0, v[9], nn[9];
+    for (uint64_t i = 0; i < n; ++i) {
+        vr::refit::transform_tri(a, b.tris[i].v, b.normals[i].n, v, nn);
+        vr::refit::validate_tri(v, nn, val.nonfinite, max_abs, val.not_finite);
+    }
+    if (val.nonfinite) return fail(VR_ERROR_UNSUPPORTED, kOverflow);
+    if (!s->plans[mi].built) {
+        const int rc = build_update_plan(s, mi);
+        if (rc) return rc;
+    }
+    for (uint64_t i = 0; i < n; ++i)
+        vr::refit::transform_tri(a, b.tris[i].v, b.normals[i].n, s->tris[tri_base + i].v, s->normals[tri_base + i].n);
+    refit_host(s, mi, max_abs, val);
+    return VR_OK;
+}
+
+int transform_mesh_device(vr_scene* s, uint32_t mi, uint64_t n, const vr::refit::Affine& a, hipStream_t st) {
+    VR_HIP(hipSetDevice(s->device));
+    vr_scene::UpdatePlan& p = s->plans[mi];
+    if (!p.built) {
+        const int rc = build_update_plan(s, mi);
+        if (rc) return rc;
+    }
+    vr_scene::MeshBase& b = s->bases[mi];
+    const size_t half = (size_t)n * sizeof(vr::TriVerts);
+    static_assert(sizeof(vr::TriVerts) == sizeof(vr::TriNormals), "the base holds both arrays, one after the other");
+    if (!b.d_base) {
+        VR_HIP(hipMalloc(&b.d_base, 2 * half));
+        s->device_bytes += 2 * half;
+    }
+    const int32_t tri_base = s->mesh_tri_base[mi];
+    vr::TriVerts* tris = const_cast<vr::TriVerts*>(s->dev.tris) + tri_base;
+    vr::TriNormals* normals = const_cast<vr::TriNormals*>(s->dev.normals) + tri_base;
+    const vr::TriVerts* base_tris = (const vr::TriVerts*)b.d_base;
+    const vr::TriNormals* base_normals = (const vr::TriNormals*)((const char*)b.d_base + half);
+    if (!b.current) {
+        VR_HIP(hipMemcpyAsync(b.d_base, tris, half, hipMemcpyDeviceToDevice, st));
+        VR_HIP(hipMemcpyAsync((char*)b.d_base + half, normals, half, hipMemcpyDeviceToDevice, st));
+    }
+    auto dev = [](int e, const char* what) {
+        return fail(VR_ERROR_DEVICE, std::string(what) + ": " + hipGetErrorString((hipError_t)e));
+    };
+    // errors come before anything is modified: the reduction over the transformed base is read back first
+    int e = vr::launch_transform_validate(base_tris, base_normals, n, a, p.d_valid, st);
+    if (e) return dev(e, "scene transform (validate)");
+    vr::refit::Validation val{};
+    VR_HIP(hipMemcpyAsync(&val, p.d_valid, sizeof val, hipMemcpyDeviceToHost, st));
+    VR_HIP(hipStreamSynchronize(st));
+    b.current = true;  // the copy above has completed
+    if (val.nonfinite) return fail(VR_ERROR_UNSUPPORTED, kOverflow);
+    e = vr::launch_transform_write(base_tris, base_normals, n, a, tris, normals, st);
+    if (e) return dev(e, "scene transform (write)");
+    return refit_device(s, mi, val, st);
+}
+
+}  // namespace
+
+int vr_scene_set_camera(vr_scene* s, vr_vec3 location) {
+    if (!s) return fail(VR_ERROR_INVALID_ARGUMENT, "null scene");
+    if (!std::isfinite(location.x) || !std::isfinite(location.y) || !std::isfinite(location.z))
+        return fail(VR_ERROR_INVALID_ARGUMENT, "scene edit: a camera coordinate is not finite");
+    s->camera[0] = location.x;
+    s->camera[1] = location.y;
+    s->camera[2] = location.z;
+    std::memcpy(s->dev.camera, s->camera, sizeof s->dev.camera);
+    update_base_extent(s);
+    update_scalars(s);
+    return VR_OK;
+}
+
+int vr_scene_update_primitives(vr_scene* s, uint32_t first, uint32_t count, const vr_primitive_desc* prims) {
+    if (!s) return fail(VR_ERROR_INVALID_ARGUMENT, "null scene");
+    if ((uint64_t)first + count > s->prim_rows.size())
+        return fail(VR_ERROR_INVALID_ARGUMENT, "scene edit: primitive range past primitive_count");
+    if (count == 0) return VR_OK;
+    if (!prims) return fail(VR_ERROR_INVALID_ARGUMENT, "scene edit: null primitive array");
+    for (uint32_t k = 0; k < count; ++k) {
+        if (prims[k].kind != VR_PRIMITIVE_PLANE && prims[k].kind != VR_PRIMITIVE_SPHERE)
+            return fail(VR_ERROR_INVALID_ARGUMENT, "scene edit: unknown primitive kind");
+        if (prims[k].material >= s->desc_materials)
+            return fail(VR_ERROR_INVALID_ARGUMENT, "scene edit: primitive material out of range");
+    }
+    uint32_t lo = UINT32_MAX, hi = 0;  // the rows that change
+    for (uint32_t k = 0; k < count; ++k)
+        for (uint32_t row : s->prim_rows[first + k]) {
+            const vr::Prim old = s->prims[row];
+            (void)prim_row(prims[k], old.object, old.position, s->prims[row]);  // the kind was checked above
+            lo = std::min(lo, row);
+            hi = std::max(hi, row);
+        }
+    update_base_extent(s);
+    update_scalars(s);
+    if (lo > hi) return VR_OK;  // entries that no list refers to
+    return copy_rows(s, s->dev.prims, sizeof(vr::Prim), lo, &s->prims[lo], (size_t)(hi - lo + 1));
+}
+
+int vr_scene_update_material(vr_scene* s, uint32_t index, const vr_material_desc* material) {
+    if (!s || !material) return fail(VR_ERROR_INVALID_ARGUMENT, "null scene or material");
+    if (index >= s->desc_materials) return fail(VR_ERROR_INVALID_ARGUMENT, "scene edit: material index out of range");
+    vr::Material row;
+    if (const char* why = material_row(*material, row)) return fail(VR_ERROR_INVALID_ARGUMENT, why);
+    s->materials[index] = row;
+    update_material_scalars(s);
+    update_scalars(s);
+    return copy_rows(s, s->dev.materials, sizeof(vr::Material), index, &s->materials[index], 1);
+}
+
+int vr_scene_set_lights(vr_scene* s, const vr_integrator_desc* integrator) {
+    if (!s) return fail(VR_ERROR_INVALID_ARGUMENT, "null scene");
+    const int32_t kind = integrator ? integrator->kind : (int32_t)VR_INTEGRATOR_SIMPLE_RANDOM;
+    if (kind != s->dev.integrator || (integrator && (int64_t)integrator->light_count != s->dev.light_count))
+        return fail(VR_ERROR_INVALID_ARGUMENT, "scene edit: integrator kind or light_count differs from the scene's");
+    if (kind != VR_INTEGRATOR_WHITTED) return VR_OK;
+    std::vector<vr::Material> rows;
+    std::vector<double> dirs;
+    if (const char* why = light_rows(*integrator, rows, dirs)) return fail(VR_ERROR_INVALID_ARGUMENT, why);
+    std::copy(rows.begin(), rows.end(), s->materials.begin() + s->dev.light_base);
+    s->light_dirs = dirs;
+    const int rc = copy_rows(s, s->dev.materials, sizeof(vr::Material), (size_t)s->dev.light_base, rows.data(), rows.size());
+    return rc ? rc : copy_rows(s, s->dev.light_dirs, sizeof(double), 0, dirs.data(), dirs.size());
+}
+
+int vr_scene_transform_mesh(vr_scene* s, uint32_t mesh, const double matrix[12], void* stream) {
+    if (!s || !matrix) return fail(VR_ERROR_INVALID_ARGUMENT, "null scene or matrix");
+    if (mesh >= s->leaf_order.size()) return fail(VR_ERROR_INVALID_ARGUMENT, "scene transform: bad mesh index");
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(matrix[i]))
+            return fail(VR_ERROR_INVALID_ARGUMENT, "scene transform: a matrix entry is not finite");
+    const uint64_t n = s->leaf_order[mesh].size();
+    if (n == 0) return VR_OK;  // an empty mesh stays empty
+    const vr::refit::Affine a = affine_of(matrix);
+    if (s->host_only) return transform_mesh_host(s, mesh, n, a);
+    return transform_mesh_device(s, mesh, n, a, (hipStream_t)stream);
+}
+
+int vr_scene_primitives(const vr_scene* s, void* out, uint32_t* count) {
+    if (!s || (!out && !count)) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
+    if (count) *count = (uint32_t)s->prims.size();
+    return out ? dump_rows(s, s->dev.prims, s->prims.data(), s->prims.size() * sizeof(vr::Prim), out) : VR_OK;
+}
+
+int vr_scene_materials(const vr_scene* s, void* out, uint32_t* count) {
+    if (!s || (!out && !count)) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
+    if (count) *count = (uint32_t)s->materials.size();
+    return out ? dump_rows(s, s->dev.materials, s->materials.data(), s->materials.size() * sizeof(vr::Material), out) : VR_OK;
+}
+
+int vr_scene_get_camera(const vr_scene* s, vr_vec3* out) {
+    if (!s || !out) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
+    *out = vr_vec3{s->camera[0], s->camera[1], s->camera[2]};
+    return VR_OK;
 }
 
 int vr_scene_wide_nodes(const vr_scene* s, void* out) {

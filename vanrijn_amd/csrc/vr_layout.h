@@ -68,6 +68,7 @@ struct alignas(16) TriNormals {
     double pad;
 };
 
+// (vr_scene_materials dumps these rows, vr_scene_primitives the Prim rows below: the sizes are ABI)
 struct Material {
     int32_t kind;  // 0 Lambertian, 1 Reflective, 2 Phong, 3 smooth transparent dielectric
     int32_t n;     // spectrum sample count (colour; the refractive index for the dielectric)
@@ -98,6 +99,9 @@ struct Prim {
     double pre[3];
     double scalar2;
 };
+
+static_assert(sizeof(Material) == 1080, "Material must be 1,080 B (vr_scene_materials)");
+static_assert(sizeof(Prim) == 128, "Prim must be 128 B (vr_scene_primitives)");
 
 struct Bvh {
     double root_box[6];  // bounds of the whole tree (tested first, as the reference's root)
@@ -355,6 +359,16 @@ int launch_refit_gather(const double* verts, const double* norms, const uint32_t
 int launch_refit_levels(Node* nodes, Node4* nodes4, const TriVerts* tris, const int32_t* items, const uint32_t* host_first,
                         uint32_t levels, void* stream);
 int launch_refit_root(Bvh* bvh, const Node* nodes, const TriVerts* tris, void* stream);
+// vr_scene_transform_mesh: the Validation of the `n` base records transformed by `a` (vr_refit.h
+// refit::Affine) into out4 (zeroed first), and slot i < n of tris / normals set to the transform of
+// base record i (rank and padding stay)
+namespace refit {
+struct Affine;
+}
+int launch_transform_validate(const TriVerts* base_tris, const TriNormals* base_normals, uint64_t n,
+                              const refit::Affine& a, unsigned long long* out4, void* stream);
+int launch_transform_write(const TriVerts* base_tris, const TriNormals* base_normals, uint64_t n, const refit::Affine& a,
+                           TriVerts* tris, TriNormals* normals, void* stream);
 #ifdef VR_SPLIT_PROBE  // analysis builds (vr_render.hip)
 int launch_trace_probe(const RenderArgs& args, int stack_depth, int minw, bool s16, int grid, void* stream);
 #endif

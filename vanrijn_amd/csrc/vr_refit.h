@@ -64,6 +64,38 @@ __host__ __device__ inline bool tri_shading_finite(const double* v, const double
     return (d[0] > m6 && d[1] > m6 && d[2] > m6) || (d[0] < -m6 && d[1] < -m6 && d[2] < -m6);
 }
 
+// vr_scene_transform_mesh: the row-major 3x4 matrix [A | t] and the cofactor matrix K of A, which
+// the host computes once (vr_host.cpp affine_of)
+struct Affine {
+    double m[12];
+    double k[9];
+};
+
+// One triangle of vr_scene_transform_mesh: base vertices / normals (9 f64 each) -> transformed.  The
+// order of operations is the header's, with no contraction (the build's -ffp-contract=off), so the
+// host form, the kernels and a restatement elsewhere give the same bits.
+__host__ __device__ inline void transform_tri(const Affine& a, const double* bv, const double* bn, double* v, double* nn) {
+    for (int p = 0; p < 3; ++p) {
+        const double x = bv[3 * p], y = bv[3 * p + 1], z = bv[3 * p + 2];
+        const double nx = bn[3 * p], ny = bn[3 * p + 1], nz = bn[3 * p + 2];
+        for (int c = 0; c < 3; ++c) {
+            v[3 * p + c] = ((a.m[4 * c] * x + a.m[4 * c + 1] * y) + a.m[4 * c + 2] * z) + a.m[4 * c + 3];
+            nn[3 * p + c] = (a.k[3 * c] * nx + a.k[3 * c + 1] * ny) + a.k[3 * c + 2] * nz;
+        }
+    }
+}
+
+// one triangle's share of a Validation (max_abs as a double; the reductions store its bits)
+__host__ __device__ inline void validate_tri(const double* v, const double* nn, unsigned long long& nonfinite,
+                                             double& max_abs, unsigned long long& not_finite) {
+    for (int i = 0; i < 9; ++i) {
+        if (!isfinite(v[i])) ++nonfinite;
+        const double a = fabs(v[i]);
+        max_abs = max_abs < a ? a : max_abs;  // std::max(extent, |v|): a NaN never replaces it
+    }
+    if (!tri_shading_finite(v, nn)) ++not_finite;
+}
+
 // box[c] of both children of a binary node: a leaf child's triangle box, an interior child's union
 __host__ __device__ inline void refit_node(Node* nodes, const TriVerts* tris, int32_t i) {
     Node& n = nodes[i];

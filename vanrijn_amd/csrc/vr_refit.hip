@@ -13,6 +13,9 @@
 //              agent-scope release / acquire per hand-off, and fail as a silently stale box).
 //   root       Bvh::root_box and root_box32 of the mesh's root record
 //
+// vr_scene_transform_mesh runs the same refit after two passes of its own over the mesh's resident
+// base records instead of validate and gather: transform-validate and transform-write.
+//
 // The per-record arithmetic lives in vr_refit.h, shared with the host refit of VR_SCENE_HOST_ONLY
 // scenes: min / max and outward rounding only, so the stored bits do not depend on who computed them.
 #include <hip/hip_runtime.h>
@@ -28,23 +31,9 @@ namespace refit {
 
 constexpr int kBlock = 256;
 
-__global__ void __launch_bounds__(kBlock) validate_kernel(const double* __restrict__ verts, const double* __restrict__ norms,
-                                                          uint64_t n, Validation* out) {
-    unsigned long long nonfinite = 0, not_finite = 0;
-    double max_abs = 0.0;
-    for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < n; t += (uint64_t)gridDim.x * kBlock) {
-        double v[9], nn[9];
-        for (int i = 0; i < 9; ++i) {
-            v[i] = verts[9 * t + i];
-            nn[i] = norms[9 * t + i];
-        }
-        for (int i = 0; i < 9; ++i) {
-            if (!isfinite(v[i])) ++nonfinite;
-            const double a = fabs(v[i]);
-            max_abs = max_abs < a ? a : max_abs;  // std::max(extent, |v|): a NaN never replaces it
-        }
-        if (!tri_shading_finite(v, nn)) ++not_finite;
-    }
+// a workgroup's per-thread shares of a Validation into *out (zeroed before the launch)
+__device__ inline void reduce_validation(unsigned long long nonfinite, unsigned long long not_finite, double max_abs,
+                                         Validation* out) {
     __shared__ unsigned long long s_bad[kBlock], s_nf[kBlock], s_max[kBlock];
     s_bad[threadIdx.x] = nonfinite;
     s_nf[threadIdx.x] = not_finite;
@@ -63,6 +52,26 @@ __global__ void __launch_bounds__(kBlock) validate_kernel(const double* __restri
         if (s_nf[0]) atomicAdd(&out->not_finite, s_nf[0]);
         atomicMax(&out->max_abs, s_max[0]);
     }
+}
+
+__global__ void __launch_bounds__(kBlock) validate_kernel(const double* __restrict__ verts, const double* __restrict__ norms,
+                                                          uint64_t n, Validation* out) {
+    unsigned long long nonfinite = 0, not_finite = 0;
+    double max_abs = 0.0;
+    for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < n; t += (uint64_t)gridDim.x * kBlock) {
+        double v[9], nn[9];
+        for (int i = 0; i < 9; ++i) {
+            v[i] = verts[9 * t + i];
+            nn[i] = norms[9 * t + i];
+        }
+        for (int i = 0; i < 9; ++i) {
+            if (!isfinite(v[i])) ++nonfinite;
+            const double a = fabs(v[i]);
+            max_abs = max_abs < a ? a : max_abs;  // std::max(extent, |v|): a NaN never replaces it
+        }
+        if (!tri_shading_finite(v, nn)) ++not_finite;
+    }
+    reduce_validation(nonfinite, not_finite, max_abs, out);
 }
 
 // Destination records are 80 B at 16-B alignment: five dwordx4 stores each.  The last quad of a
@@ -85,6 +94,56 @@ __global__ void __launch_bounds__(kBlock) gather_kernel(const double* __restrict
     }
     tv[4] = make_double2(v[8], rank);
     tn[4] = make_double2(m[8], pad);
+}
+
+// vr_scene_transform_mesh.  The base is a copy of the mesh's 80-B records in slot order (rank and
+// padding included), so both passes read record i with five dwordx4 loads per array and need no gather.
+__device__ inline void load_base(const TriVerts* base_tris, const TriNormals* base_normals, uint64_t i, double bv[10],
+                                 double bn[10]) {
+    const double2* tv = reinterpret_cast<const double2*>(base_tris + i);
+    const double2* tn = reinterpret_cast<const double2*>(base_normals + i);
+    for (int q = 0; q < 5; ++q) {
+        const double2 a = tv[q], b = tn[q];
+        bv[2 * q] = a.x;
+        bv[2 * q + 1] = a.y;
+        bn[2 * q] = b.x;
+        bn[2 * q + 1] = b.y;
+    }
+}
+
+// the Validation of the transformed records, before anything is written
+__global__ void __launch_bounds__(kBlock) transform_validate_kernel(const TriVerts* __restrict__ base_tris,
+                                                                    const TriNormals* __restrict__ base_normals, uint64_t n,
+                                                                    Affine a, Validation* out) {
+    unsigned long long nonfinite = 0, not_finite = 0;
+    double max_abs = 0.0;
+    for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < n; t += (uint64_t)gridDim.x * kBlock) {
+        double bv[10], bn[10], v[9], nn[9];
+        load_base(base_tris, base_normals, t, bv, bn);
+        transform_tri(a, bv, bn, v, nn);
+        validate_tri(v, nn, nonfinite, max_abs, not_finite);
+    }
+    reduce_validation(nonfinite, not_finite, max_abs, out);
+}
+
+// slot i of the mesh takes the transform of base record i: five dwordx4 stores per array, as
+// gather_kernel; the last quads carry the base copy's rank and padding, which are the slot's own
+__global__ void __launch_bounds__(kBlock) transform_write_kernel(const TriVerts* __restrict__ base_tris,
+                                                                 const TriNormals* __restrict__ base_normals, uint64_t n,
+                                                                 Affine a, TriVerts* tris, TriNormals* normals) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    double bv[10], bn[10], v[9], nn[9];
+    load_base(base_tris, base_normals, i, bv, bn);
+    transform_tri(a, bv, bn, v, nn);
+    double2* tv = reinterpret_cast<double2*>(tris + i);
+    double2* tn = reinterpret_cast<double2*>(normals + i);
+    for (int q = 0; q < 4; ++q) {
+        tv[q] = make_double2(v[2 * q], v[2 * q + 1]);
+        tn[q] = make_double2(nn[2 * q], nn[2 * q + 1]);
+    }
+    tv[4] = make_double2(v[8], bv[9]);  // bit patterns, moved not computed
+    tn[4] = make_double2(nn[8], bn[9]);
 }
 
 __global__ void __launch_bounds__(kBlock) refit_level_kernel(Node* nodes, const TriVerts* tris, const int32_t* __restrict__ items,
@@ -121,6 +180,26 @@ int launch_refit_gather(const double* verts, const double* norms, const uint32_t
     const uint64_t blocks = (n + refit::kBlock - 1) / refit::kBlock;
     refit::gather_kernel<<<dim3((unsigned)blocks), dim3(refit::kBlock), 0, (hipStream_t)stream>>>(verts, norms, slot_src, n,
                                                                                                    tris, normals);
+    return (int)hipGetLastError();
+}
+
+int launch_transform_validate(const TriVerts* base_tris, const TriNormals* base_normals, uint64_t n,
+                              const refit::Affine& a, unsigned long long* out4, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(out4, 0, sizeof(refit::Validation), st);
+    if (e != hipSuccess || n == 0) return (int)e;
+    const uint64_t blocks = (n + refit::kBlock - 1) / refit::kBlock;
+    refit::transform_validate_kernel<<<dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(refit::kBlock), 0, st>>>(
+        base_tris, base_normals, n, a, reinterpret_cast<refit::Validation*>(out4));
+    return (int)hipGetLastError();
+}
+
+int launch_transform_write(const TriVerts* base_tris, const TriNormals* base_normals, uint64_t n, const refit::Affine& a,
+                           TriVerts* tris, TriNormals* normals, void* stream) {
+    if (n == 0) return 0;
+    const uint64_t blocks = (n + refit::kBlock - 1) / refit::kBlock;
+    refit::transform_write_kernel<<<dim3((unsigned)blocks), dim3(refit::kBlock), 0, (hipStream_t)stream>>>(
+        base_tris, base_normals, n, a, tris, normals);
     return (int)hipGetLastError();
 }
 

@@ -313,6 +313,35 @@ class Scene:
         return self._device_scenes[key]
 
 
+def _c_spectrum(sp, keep):
+    a = np.ascontiguousarray(sp.samples, dtype=np.float64)
+    keep.append(a)
+    return N.Spectrum(sp.shortest_wavelength, sp.longest_wavelength, a.size, a.ctypes.data_as(C.POINTER(C.c_double)))
+
+
+def _c_material(m: MaterialSpec, keep):
+    return N.MaterialDesc(m.kind, 0, _c_spectrum(m.colour, keep), m.diffuse_strength, m.reflection_strength,
+                          m.smoothness)
+
+
+def _c_integrator(integrator: WhittedIntegrator, keep):
+    lights = (N.DirectionalLightC * max(len(integrator.lights), 1))()
+    for j, li in enumerate(integrator.lights):
+        lights[j] = N.DirectionalLightC(N.Vec3(*li.direction), _c_spectrum(li.spectrum, keep))
+    keep.append(lights)
+    return N.IntegratorDesc(N.INTEGRATOR_WHITTED, len(integrator.lights), _c_spectrum(integrator.ambient_light, keep),
+                            lights)
+
+
+def _c_primitive(p):
+    """A PrimitiveSpec, or a Plane / Sphere whose `material` is a material index."""
+    if isinstance(p, Plane):
+        p = PrimitiveSpec(N.PRIMITIVE_PLANE, p.material, tuple(p.normal), float(p.distance_from_origin))
+    elif isinstance(p, Sphere):
+        p = PrimitiveSpec(N.PRIMITIVE_SPHERE, p.material, tuple(p.centre), float(p.radius))
+    return N.PrimitiveDesc(p.kind, int(p.material), N.Vec3(*p.vector), p.scalar)
+
+
 class DeviceScene:
     """Owner of a `vr_scene*` (flattened BVH resident in one GPU's HBM)."""
 
@@ -329,17 +358,12 @@ class DeviceScene:
         keep = []  # keep ctypes buffers alive during vr_scene_create
         mats = (N.MaterialDesc * max(len(spec.materials), 1))()
         for i, m in enumerate(spec.materials):
-            s = np.ascontiguousarray(m.colour.samples, dtype=np.float64)
-            keep.append(s)
-            mats[i] = N.MaterialDesc(m.kind, 0, N.Spectrum(m.colour.shortest_wavelength, m.colour.longest_wavelength,
-                                                           s.size, s.ctypes.data_as(C.POINTER(C.c_double))),
-                                     m.diffuse_strength, m.reflection_strength, m.smoothness)
+            mats[i] = _c_material(m, keep)
         prims, objs, meshes = [], [], []
         for o in spec.objects:
             if o.kind == "primitives":
                 objs.append(N.ObjectDesc(N.OBJECT_PRIMITIVE_LIST, len(prims), len(o.primitives), 0))
-                for p in o.primitives:
-                    prims.append(N.PrimitiveDesc(p.kind, p.material, N.Vec3(*p.vector), p.scalar))
+                prims += [_c_primitive(p) for p in o.primitives]
             else:
                 objs.append(N.ObjectDesc(N.OBJECT_BVH, o.mesh, 1, 0))
         for m in spec.meshes:
@@ -352,19 +376,7 @@ class DeviceScene:
         prim_arr = (N.PrimitiveDesc * max(len(prims), 1))(*prims)
         obj_arr = (N.ObjectDesc * max(len(objs), 1))(*objs)
         mesh_arr = (N.MeshDesc * max(len(meshes), 1))(*meshes)
-        ig = None
-        if spec.integrator is not None:
-            def cspec(sp):
-                a = np.ascontiguousarray(sp.samples, dtype=np.float64)
-                keep.append(a)
-                return N.Spectrum(sp.shortest_wavelength, sp.longest_wavelength, a.size,
-                                  a.ctypes.data_as(C.POINTER(C.c_double)))
-            lights = (N.DirectionalLightC * max(len(spec.integrator.lights), 1))()
-            for j, li in enumerate(spec.integrator.lights):
-                lights[j] = N.DirectionalLightC(N.Vec3(*li.direction), cspec(li.spectrum))
-            keep.append(lights)
-            ig = N.IntegratorDesc(N.INTEGRATOR_WHITTED, len(spec.integrator.lights),
-                                  cspec(spec.integrator.ambient_light), lights)
+        ig = _c_integrator(spec.integrator, keep) if spec.integrator is not None else None
         desc = N.SceneDesc(N.Vec3(*spec.camera_location), len(spec.materials), len(prims), len(meshes), len(objs),
                            mats, prim_arr, mesh_arr, obj_arr, C.pointer(ig) if ig is not None else None)
         h = C.c_void_p()
@@ -491,3 +503,79 @@ class DeviceScene:
         n = len(self.spec.meshes[mesh].vertices) if 0 <= mesh < len(self.spec.meshes) else 0
         N.check(N.lib().vr_scene_update_mesh_device(self.handle, mesh, n, C.c_void_p(vertices_ptr),
                                                     C.c_void_p(normals_ptr), C.c_void_p(stream_ptr or 0)))
+
+    # ------------------------------------------------------------------ scene edits (VR_HAS_SCENE_EDIT)
+    # Each changes THIS device scene only and blocks until it is ready; afterwards every call answers
+    # as on a scene created from the edited description, bit for bit.  Not thread-safe against other
+    # calls on this scene; its queued asynchronous work must be done.  As with update_mesh, the owning
+    # Scene / SceneSpec are not touched: other cached DeviceScenes of the same Scene, and scenes created
+    # from it later, keep the old description.
+    def set_camera(self, xyz):
+        """vr_scene_set_camera: the camera location (three finite floats).  The owning Scene /
+        SceneSpec are not touched."""
+        x, y, z = (float(c) for c in xyz)
+        N.check(N.lib().vr_scene_set_camera(self.handle, N.Vec3(x, y, z)))
+
+    def update_primitives(self, first, prims):
+        """vr_scene_update_primitives: replace entries first .. first + len(prims) - 1 of the scene's
+        primitives (numbered through all primitive lists in object order) by `prims`: PrimitiveSpec, or
+        Plane / Sphere whose `material` is a material index.  The owning Scene / SceneSpec are not
+        touched."""
+        arr = (N.PrimitiveDesc * max(len(prims), 1))(*[_c_primitive(p) for p in prims])
+        N.check(N.lib().vr_scene_update_primitives(self.handle, int(first), len(prims), arr))
+
+    def update_material(self, index, material: MaterialSpec):
+        """vr_scene_update_material: replace material `index` of the spec's materials; nan_free and the
+        kernel choice follow as on a fresh scene.  The owning Scene / SceneSpec are not touched."""
+        keep = []
+        m = _c_material(material, keep)
+        N.check(N.lib().vr_scene_update_material(self.handle, int(index), C.byref(m)))
+
+    def set_lights(self, integrator):
+        """vr_scene_set_lights: a WhittedIntegrator with as many lights as the scene's (new ambient
+        spectrum, light spectra and directions), or None on a SimpleRandomIntegrator scene (nothing
+        changes).  The owning Scene / SceneSpec are not touched."""
+        keep = []
+        ig = _c_integrator(integrator, keep) if integrator is not None else None
+        N.check(N.lib().vr_scene_set_lights(self.handle, C.byref(ig) if ig is not None else None))
+
+    def transform_mesh(self, mesh, matrix, stream_ptr=None):
+        """vr_scene_transform_mesh: mesh `mesh` becomes the image of its base geometry (creation's, or
+        the latest update_mesh's) under the row-major 3x4 matrix [A | t] (any array-like of 12 or 3x4
+        values); normals go through A's cofactor matrix.  Transforms do not compound.  Runs on the
+        device from resident records, ordered after earlier work on `stream_ptr` (None: the null
+        stream).  The owning Scene / SceneSpec are not touched."""
+        m = np.ascontiguousarray(matrix, dtype=np.float64).reshape(-1)
+        if m.size != 12:
+            raise ValueError("matrix must hold 12 values (3x4, row-major)")
+        N.check(N.lib().vr_scene_transform_mesh(self.handle, int(mesh), m.ctypes.data_as(C.c_void_p),
+                                                C.c_void_p(stream_ptr or 0)))
+
+    PRIM_DTYPE = np.dtype([("kind", "<i4"), ("material", "<i4"), ("object", "<i4"), ("position", "<i4"),
+                           ("vec", "<f8", (3,)), ("tan", "<f8", (3,)), ("cot", "<f8", (3,)), ("scalar", "<f8"),
+                           ("pre", "<f8", (3,)), ("scalar2", "<f8")])
+    MATERIAL_DTYPE = np.dtype([("kind", "<i4"), ("n", "<i4"), ("shortest", "<f8"), ("longest", "<f8"),
+                               ("diffuse", "<f8"), ("reflection", "<f8"), ("smoothness", "<f8"),
+                               ("samples", "<f8", (64,)), ("knots", "<f8", (64,)), ("inv_step", "<f8")])
+
+    def _rows(self, fn, dtype):
+        n = C.c_uint32()
+        N.check(fn(self.handle, None, C.byref(n)))
+        out = np.zeros(n.value, dtype=dtype)
+        if out.size:
+            N.check(fn(self.handle, out.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return out
+
+    def primitives(self):
+        """The primitive rows in kernel order (vr_scene_primitives), a structured array."""
+        return self._rows(N.lib().vr_scene_primitives, self.PRIM_DTYPE)
+
+    def materials(self):
+        """Every material row, the light and sky rows included (vr_scene_materials)."""
+        return self._rows(N.lib().vr_scene_materials, self.MATERIAL_DTYPE)
+
+    def camera(self):
+        """The camera location (vr_scene_get_camera), float64 [3]."""
+        v = N.Vec3()
+        N.check(N.lib().vr_scene_get_camera(self.handle, C.byref(v)))
+        return np.array([v.x, v.y, v.z])
