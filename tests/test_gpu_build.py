@@ -1,5 +1,5 @@
 """BoundingVolumeHierarchy::build_from_slice (bounding_volume_hierarchy.rs:38-74) on the device
-(VR_SCENE_DEVICE_BVH, vanrijn_amd/csrc/vr_build.hip) against the host build (vr_host.cpp), which
+(VR_SCENE_DEVICE_BVH, vanrijn_amd/csrc/vr_build.hip) against the host build (vr_host_bvh.cpp), which
 the oracle pins (tests/test_oracle_scene.py: leaf orders equal to the oracle's build).
 
 Bar: identical interior nodes (child boxes compared with ==, child links), identical leaf order

@@ -1,4 +1,4 @@
-"""VR_SCENE_INFO_NAN_FREE (vr_host.cpp shading_finite), host-only scenes (CPU).
+"""VR_SCENE_INFO_NAN_FREE (vr_host_scene.cpp shading_finite), host-only scenes (CPU).
 
 The early stop of zero-throughput paths is allowed only where every continuation is provably
 finite ("NaN fidelity"): each traced triangle's vertex normals strictly on

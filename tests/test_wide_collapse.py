@@ -1,6 +1,6 @@
 """The 4-wide traversal tree's collapse (CPU: host-only scenes, no GPU).
 
-The SAH-optimal DP collapse (vr_host.cpp WideBuilder; VR_SCENE_GREEDY_COLLAPSE builds the greedy one) may take a node's DP expansion
+The SAH-optimal DP collapse (vr_host_bvh.cpp WideBuilder; VR_SCENE_GREEDY_COLLAPSE builds the greedy one) may take a node's DP expansion
 only where its subtree's stack bound keeps the greedy tree's LDS stack class (24 / 32 / 48 entries of
 the render kernel's traversal stack): the stack bound never moves to a larger class, and the DP tree
 never has more wide nodes than the greedy one (fuller nodes).  Which tree is walked does not change

@@ -1,5 +1,5 @@
 // vr_build.hip -- BoundingVolumeHierarchy::build_from_slice (bounding_volume_hierarchy.rs:38-74)
-// on the device, producing exactly the host build's flattened BVH (vr_host.cpp BvhBuilder):
+// on the device, producing exactly the host build's flattened BVH (vr_host_bvh.cpp Builder):
 // the same pre-order node array, the same leaf order, the same child boxes.
 //
 // The reference splits every node of n > 1 triangles at n / 2 after sorting its triangles by
@@ -207,7 +207,7 @@ __global__ void fill_wide_kernel(const Node* bin, const int32_t* desc, uint64_t 
 
 // ------------------------------------------------------------------------------------------------
 // The default traversal tree on the device (VR_SCENE_DEVICE_SAH): the binned-SAH binary tree of
-// vr_host.cpp SahBuilder, built top-down one level at a time, one workgroup per segment of the
+// vr_host_bvh.cpp Builder (sah), built top-down one level at a time, one workgroup per segment of the
 // level.  Its input is the reference-order triangle array the median build above leaves (each
 // TriVerts carries its reference in-order rank, which breaks distance ties);
 // its output is the SAH binary tree and the triangles permuted into its leaf order.  The tree

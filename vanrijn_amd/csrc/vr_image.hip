@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void export_buffer_kernel(const double* __rest
 }
 // A fresh buffer after exactly one sample per pixel (vr_partial_render_scene): weight 1, weight
 // bias 0, and colour / colour_bias follow from colour_sum alone, so only the sums cross PCIe
-// (24 of the 88 B per pixel); the host expands them (vr_host.cpp expand_fresh_one_sample).
+// (24 of the 88 B per pixel); the host expands them (vr_host.cpp vr_render_tile, fresh1).
 __global__ __launch_bounds__(256) void export_sums_kernel(const double* __restrict__ state, uint64_t npix,
                                                           double* __restrict__ sums) {
     const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void import_buffer_kernel(const double* __rest
     b[3] = planar[10 * npix + p];
 }
 
-// The film (vr_film, vr_host.cpp): the reference's full-image AccumulationBuffer resident on the
+// The film (vr_film, vr_host_film.cpp): the reference's full-image AccumulationBuffer resident on the
 // device, 32 B per pixel {colour X, Y, Z, weight}, row-major -- the shape of the sums half of the
 // records, so a lane moves a pixel as two 16-byte accesses and consecutive lanes (consecutive
 // columns of a tile row) touch contiguous lines on both sides.

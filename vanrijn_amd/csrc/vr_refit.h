@@ -1,4 +1,4 @@
-// vr_refit.h -- the per-record steps of vr_scene_update_mesh, shared by the host refit (vr_host.cpp,
+// vr_refit.h -- the per-record steps of vr_scene_update_mesh, shared by the host refit (vr_host_edit.cpp,
 // VR_SCENE_HOST_ONLY scenes) and the device refit (vr_refit.hip): one definition, so both store the
 // same bits.  Every step is exact (min / max and outward rounding only), so a refitted tree holds
 // what a bottom-up build over the same topology would store.
@@ -24,7 +24,7 @@ struct Validation {
 __host__ __device__ inline double dmin(double a, double b) { return fmin(a, b); }  // NaN-ignoring, as f64::min
 __host__ __device__ inline double dmax(double a, double b) { return fmax(a, b); }
 
-// f32 copies of f64 bounds rounded outward (vr_host.cpp round_lower / round_upper, the same values)
+// f32 copies of f64 bounds rounded outward (vr_host_bvh.cpp round_lower / round_upper, the same values)
 __host__ __device__ inline float round_lower32(double v) {
     float f = (float)v;
     if ((double)f > v) f = nextafterf(f, -INFINITY);
@@ -44,7 +44,7 @@ __host__ __device__ inline void tri_box(const double* v, double box[6]) {
     }
 }
 
-// one triangle of vr_host.cpp shading_finite: the same f64 operations in the same order
+// one triangle of vr_host_scene.cpp shading_finite: the same f64 operations in the same order
 __host__ __device__ inline bool tri_shading_finite(const double* v, const double* nn) {
     for (int i = 0; i < 9; ++i)
         if (!isfinite(v[i]) || !isfinite(nn[i]) || fabs(v[i]) > 1e100 || fabs(nn[i]) > 1e100) return false;
@@ -65,7 +65,7 @@ __host__ __device__ inline bool tri_shading_finite(const double* v, const double
 }
 
 // vr_scene_transform_mesh: the row-major 3x4 matrix [A | t] and the cofactor matrix K of A, which
-// the host computes once (vr_host.cpp affine_of)
+// the host computes once (vr_host_edit.cpp affine_of)
 struct Affine {
     double m[12];
     double k[9];

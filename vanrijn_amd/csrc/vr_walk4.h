@@ -200,7 +200,7 @@ __device__ __forceinline__ bool walk4(const DeviceScene& S, const RayPre& pre, u
                 if (ANY ? next == (uint32_t)kEmptyChild : j == 0) {
                     next = child;
                 } else {
-                    // (at most wide_stack entries are ever live: vr_host.cpp WideBuilder::stack)
+                    // (at most wide_stack entries are ever live: vr_host_bvh.cpp WideBuilder::stack)
                     st[sp * 256 + tid] = child;
                     // the entry distance rounded down (its two low bits cleared; 0 for a negative one)
                     if (!ANY) st[(STACK + sp) * 256 + tid] = kj & ~3u;
