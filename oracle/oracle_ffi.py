@@ -97,6 +97,9 @@ def lib():
             "orc_colour_xyz_from_linear_rgb": (None, [p, p]),
             "orc_sky_intensity": (d, [p, d]),
             "orc_tone_map": (None, [p, u64, p]),
+            "orc_fresnel": (None, [p, d, d, p, p, p, p]),
+            "orc_material_bsdf": (C.c_int, [i32, d, d, i32, p, d, d, d, p, p, d, d, p]),
+            "orc_material_sample": (C.c_int, [i32, d, d, i32, p, d, d, d, p, d, u64, u64, p, p]),
             "orc_scene_set_whitted": (C.c_int, [p, d, d, i32, p, i32, p, p, p, p, p]),
             "orc_ray_for_pixel": (None, [p, u64, u64, u64, u64, d, d, p, p]),
             "orc_update_pixel": (None, [p, p, p, p, p, d, d, d]),
@@ -343,6 +346,42 @@ def ray_for_pixel(camera, width, height, row, column, ux, uy):
     o, d = np.zeros(3), np.zeros(3)
     lib().orc_ray_for_pixel(_ptr(f64(camera, 3)), width, height, row, column, ux, uy, _ptr(o), _ptr(d))
     return o, d
+
+
+# ---------------------------------------------------------------- materials
+def fresnel(w_i, eta1, eta2):
+    """-> (rdir, tdir, R, T)."""
+    rdir, tdir, rt = np.zeros(3), np.zeros(3), np.zeros(2)
+    lib().orc_fresnel(_ptr(f64(w_i, 3)), eta1, eta2, _ptr(rdir), _ptr(tdir), _ptr(rt[0:1]), _ptr(rt[1:2]))
+    return rdir, tdir, float(rt[0]), float(rt[1])
+
+
+def _material_args(kind, shortest, longest, samples, diffuse, reflection, smoothness):
+    s = f64(samples)
+    return s, (kind, shortest, longest, s.size, _ptr(s), diffuse, reflection, smoothness)
+
+
+def material_bsdf(kind, shortest, longest, samples, diffuse, reflection, smoothness, w_o, w_i, wavelength, intensity):
+    """Material::bsdf(w_o, w_i, Photon{wavelength, intensity}).intensity."""
+    s, args = _material_args(kind, shortest, longest, samples, diffuse, reflection, smoothness)
+    out = np.zeros(1)
+    assert lib().orc_material_bsdf(*args, _ptr(f64(w_o, 3)), _ptr(f64(w_i, 3)), wavelength, intensity, _ptr(out)) == 0
+    return float(out[0])
+
+
+def material_sample(kind, shortest, longest, samples, diffuse, reflection, smoothness, w_i, wavelength, base,
+                    first_draw):
+    """Material::sample from draw `first_draw` of stream `base` -> (w_o, pdf, draws consumed)."""
+    s, args = _material_args(kind, shortest, longest, samples, diffuse, reflection, smoothness)
+    w_o, pdf = np.zeros(3), np.zeros(1)
+    draws = lib().orc_material_sample(*args, _ptr(f64(w_i, 3)), wavelength, base, first_draw, _ptr(w_o), _ptr(pdf))
+    assert draws >= 0
+    return w_o, float(pdf[0]), draws
+
+
+def stream_bool(base, k):
+    """rand 0.7's Standard bool from draw k of a stream: the draw's top bit."""
+    return bool(lib().orc_stream_draw(base, k) >> 63)
 
 
 # ---------------------------------------------------------------- scene

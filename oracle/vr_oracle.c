@@ -1201,6 +1201,49 @@ static photon material_bsdf(const orc_material* m, v3 w_o, v3 w_i, photon in) {
     return out;
 }
 
+/* ---- the three statics above, exported unchanged for tests/test_oracle_materials.py ---- */
+void orc_fresnel(const double w_i[3], double eta1, double eta2, double rdir[3], double tdir[3], double* R, double* T) {
+    fresnel_result f = fresnel(ld(w_i), eta1, eta2);
+    st(rdir, f.rdir);
+    st(tdir, f.tdir);
+    *R = f.R;
+    *T = f.T;
+}
+static int material_from_args(orc_material* m, int32_t kind, double shortest, double longest, int32_t n,
+                              const double* samples, double diffuse, double reflection, double smoothness) {
+    if (n < 1 || n > 64) return -1;
+    memset(m, 0, sizeof *m);
+    m->kind = kind;
+    m->shortest = shortest;
+    m->longest = longest;
+    m->n = n;
+    memcpy(m->s, samples, sizeof(double) * n);
+    m->diffuse = diffuse;
+    m->reflection = reflection;
+    m->smoothness = smoothness;
+    return 0;
+}
+int orc_material_bsdf(int32_t kind, double shortest, double longest, int32_t n, const double* samples, double diffuse,
+                      double reflection, double smoothness, const double w_o[3], const double w_i[3], double wavelength,
+                      double intensity, double* out) {
+    orc_material m;
+    if (material_from_args(&m, kind, shortest, longest, n, samples, diffuse, reflection, smoothness)) return -1;
+    photon in = {wavelength, intensity};
+    *out = material_bsdf(&m, ld(w_o), ld(w_i), in).intensity;
+    return 0;
+}
+int orc_material_sample(int32_t kind, double shortest, double longest, int32_t n, const double* samples, double diffuse,
+                        double reflection, double smoothness, const double w_i[3], double wavelength, uint64_t base,
+                        uint64_t first_draw, double w_o[3], double* pdf) {
+    orc_material m;
+    if (material_from_args(&m, kind, shortest, longest, n, samples, diffuse, reflection, smoothness)) return -1;
+    orc_rng rng = {base, first_draw};
+    v3 out;
+    material_sample(&m, ld(w_i), wavelength, &rng, &out, pdf);
+    st(w_o, out);
+    return (int)(rng.k - first_draw);
+}
+
 typedef struct path_ctx {
     const orc_scene* s;
     trace_ctx* cx;

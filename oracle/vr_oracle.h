@@ -19,6 +19,8 @@
  *   - UNPINNED (the reference has no tests for them and cannot be built here: no Rust
  *     toolchain): BVH traversal, sampler, integrator, materials,
  *     reflection_from_linear_rgb, CMF values, whole images.  Restated line by line instead.
+ *     The materials are held since to a second restatement in f64 and 50-digit arithmetic
+ *     (tests/material_reference.py, tests/test_oracle_materials.py).
  *   - The reference draws from rand 0.7's ThreadRng (ChaCha, reseeded from OS entropy, cannot be
  *     seeded: SURVEY.md F4).  The oracle and the product both draw from the counter-based
  *     "vr-hash32 v2" stream defined below; the u64 -> f64 maps follow rand 0.7's Standard and
@@ -105,6 +107,20 @@ void orc_update_pixel(double colour[3], double sum[3], double bias[3], double* w
 void orc_merge_tile(uint64_t dst_width, double* dst_colour, double* dst_weight, uint64_t start_row,
                     uint64_t start_column, uint64_t tile_h, uint64_t tile_w, const double* src_colour,
                     const double* src_weight);
+
+/* ---- materials, exported for tests/test_oracle_materials.py (thin wrappers of the statics the
+ * integrators call; a material is given as orc_scene_add_material's arguments) ---- */
+/* fresnel (smooth_transparent_dialectric.rs:15-59) */
+void orc_fresnel(const double w_i[3], double eta1, double eta2, double rdir[3], double tdir[3], double* R, double* T);
+/* Material::bsdf(w_o, w_i, Photon{wavelength, intensity}).intensity into *out; -1 on a bad spectrum */
+int orc_material_bsdf(int32_t kind, double shortest, double longest, int32_t n, const double* samples, double diffuse,
+                      double reflection, double smoothness, const double w_o[3], const double w_i[3], double wavelength,
+                      double intensity, double* out);
+/* Material::sample(w_i, photon) drawing from stream `base` at draw `first_draw`: the direction and
+ * pdf; returns the number of draws consumed, -1 on a bad spectrum */
+int orc_material_sample(int32_t kind, double shortest, double longest, int32_t n, const double* samples, double diffuse,
+                        double reflection, double smoothness, const double w_i[3], double wavelength, uint64_t base,
+                        uint64_t first_draw, double w_o[3], double* pdf);
 
 /* ---- scene ---- */
 typedef struct orc_scene orc_scene;
