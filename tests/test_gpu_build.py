@@ -12,6 +12,8 @@ import time
 import numpy as np
 import pytest
 
+import magnitude_scenes as M
+from scene_update_checks import check_refit
 from vanrijn_amd import scenes
 from vanrijn_amd.render import Tile, render_tile_device
 from vanrijn_amd.scene import LambertianMaterial, Mesh, Scene, Spectrum, BoundingVolumeHierarchy
@@ -19,12 +21,12 @@ from vanrijn_amd.scene import LambertianMaterial, Mesh, Scene, Spectrum, Boundin
 pytestmark = pytest.mark.gpu
 
 
-def _mesh_scene(v):
+def _mesh_scene(v, camera=(0.0, 0.0, -5.0)):
     v = np.asarray(v, dtype=np.float64).reshape(-1, 3, 3)
     n = np.zeros_like(v)
     n[..., 2] = 1.0
     mat = LambertianMaterial(Spectrum.grey(0.5), 0.5)
-    return Scene((0.0, 0.0, -5.0), [BoundingVolumeHierarchy.build(Mesh(v, n, mat))])
+    return Scene(camera, [BoundingVolumeHierarchy.build(Mesh(v, n, mat))])
 
 
 def _random_mesh(rng, n, ties=False, flat=False):
@@ -37,7 +39,7 @@ def _random_mesh(rng, n, ties=False, flat=False):
     return v
 
 
-def _compare(scene):
+def _compare(scene, render=True):
     host = scene.device_scene(0, host_only=True, reference_bvh=True)
     dev = scene.device_scene(0, device_bvh=True)
     hi, di = host.info(), dev.info()
@@ -50,7 +52,8 @@ def _compare(scene):
         assert np.array_equal(host.leaf_order(m), dev.leaf_order(m))
     # the render kernel's 4-wide trees differ (host: surface-area collapse of the SAH tree;
     # device: parity collapse of the median-split tree) -- the images may not
-    _render_equal(scene.device_scene(0), dev)
+    if render:
+        _render_equal(scene.device_scene(0), dev)
     assert 0 < di["wide_node_count"] <= max(1, di["node_count"]) or di["node_count"] == 0
     return dev
 
@@ -77,6 +80,32 @@ def test_device_build_matches_host_random(n):
 def test_device_build_matches_host_degenerate(kind):
     rng = np.random.default_rng(11)
     _compare(_mesh_scene(_random_mesh(rng, 3000, ties=kind == "ties", flat=kind == "flat")))
+
+
+@pytest.mark.parametrize("regime", M.BUILD_REGIMES, ids=M.regime_id)
+@pytest.mark.parametrize("kind", [257, 3000, "ties"])
+def test_device_build_matches_host_at_magnitude(kind, regime, oracle):
+    """The same meshes through x -> S x + T (tests/magnitude_scenes.py): box centres f32 does not
+    resolve, bounds in the f32 denormal range and beyond FLT_MAX.  The median build works on f64
+    boxes: nodes, boxes and leaf order equal the host's; and the 4-wide tree that fill_wide_kernel
+    rounds outward with __double2float_rd / ru is held to the host's nextafter by check_refit.
+    Rendered only where the oracle was checked, and only if it shows a camera hit."""
+    S, T = regime
+    n = 3000 if kind == "ties" else kind
+    v = M.mapped(_random_mesh(np.random.default_rng(11 + n), n, ties=kind == "ties"), S, T)
+    scene = _mesh_scene(v, camera=tuple(M.mapped((0.0, 0.0, -5.0), S, T)))
+    render = False
+    if regime in M.RENDERED:
+        cam = scene.spec().camera_location  # one row of pixel centres through the middle of the frame
+        rays = [oracle.ray_for_pixel(cam, 48, 40, 20, col, 0.5, 0.5) for col in range(48)]
+        hits, _ = oracle.OracleScene(scene.spec()).trace([r[0] for r in rays], [r[1] for r in rays],
+                                                         oracle.MODE_REFERENCE)
+        render = any(h.valid for h in hits)
+        assert render  # the camera moves with the mesh: the view is the control's
+    dev = _compare(scene, render=render)
+    nn = np.zeros_like(v)
+    nn[..., 2] = 1.0
+    check_refit(dev, [(v, nn)])
 
 
 def test_device_build_bunny_renders_identically():

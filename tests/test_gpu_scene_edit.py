@@ -11,6 +11,7 @@ import copy
 import numpy as np
 import pytest
 
+import magnitude_scenes as M
 from scene_edit_checks import IDENTITY, MATRICES, OVERFLOW, SINGULAR, edited_spec, rotation_about, rows_equal, transformed
 from scene_update_checks import assert_dumps_equal, check_refit, dumps
 from vanrijn_amd import _native as N
@@ -74,6 +75,33 @@ def test_device_built_topologies(n, flags):
     for name in ("rotation", "reflection"):
         ds.transform_mesh(0, MATRICES[name])
         check_refit(ds, [transformed(MATRICES[name], a, _normals(a))], before)
+
+
+@pytest.mark.parametrize("flags", ["device_bvh", "device_sah"])
+@pytest.mark.parametrize("regime", M.REFIT_REGIMES, ids=M.regime_id)
+def test_transform_into_each_magnitude_and_back(regime, flags):
+    """The transform kernels and the refit they start, where the bounds are beyond what f32 resolves,
+    in its denormal range, all 0 or the smallest denormal, or beyond FLT_MAX (tests/magnitude_scenes.py):
+    a translation by T and a uniform scale by S carry a unit mesh from the control into the regime, and
+    the identity carries it back; extent and nan_free are a fresh scene's."""
+    a = np.random.default_rng(257).normal(size=(257, 3, 3))
+    ds = DeviceScene(_random_scene(a).spec(), 0, **FLAG_SETS[flags])
+    before = check_refit(ds, [(a, _normals(a))])
+    home = {key: ds.info()[key] for key in ("extent", "nan_free")}
+    m = M.map_matrix(*regime)
+    w, wn = transformed(m, a, _normals(a))
+    assert np.array_equal(w, M.mapped(a, *regime))
+    ds.transform_mesh(0, m)
+    check_refit(ds, [(w, wn)], before)
+    mat = LambertianMaterial(Spectrum.grey(0.5), 0.5)
+    fresh = DeviceScene(Scene((0.0, 0.0, -5.0), [BoundingVolumeHierarchy.build(Mesh(w, wn, mat))]).spec(), 0,
+                        **FLAG_SETS[flags])
+    check_refit(fresh, [(w, wn)])
+    for key in ("extent", "nan_free"):
+        assert ds.info()[key] == fresh.info()[key], key
+    ds.transform_mesh(0, IDENTITY)
+    check_refit(ds, [transformed(IDENTITY, a, _normals(a))], before)
+    assert {key: ds.info()[key] for key in home} == home
 
 
 @pytest.mark.parametrize("flags", ["default", "device_bvh", "device_sah"])

@@ -9,6 +9,7 @@ the new geometry -- the closest hit depends only on each triangle's own box and 
 import numpy as np
 import pytest
 
+import magnitude_scenes as M
 from scene_update_checks import assert_dumps_equal, check_refit, dumps
 from vanrijn_amd import _native as N
 from vanrijn_amd import scenes
@@ -67,6 +68,35 @@ def test_device_built_topologies(n, flags):
     before = check_refit(ds, [(a, _normals(a))])
     ds.update_mesh(0, b, _normals(b))
     check_refit(ds, [(b, _normals(b))], before)
+
+
+@pytest.mark.parametrize("flags", ["device_bvh", "device_sah"])
+@pytest.mark.parametrize("regime", M.REFIT_REGIMES, ids=M.regime_id)
+def test_device_built_topologies_at_magnitude(regime, flags):
+    """write_level_kernel / sah_level_kernel / fill_wide_kernel on a fresh scene, and the refit kernels
+    after update_mesh (host arrays, then device arrays), where the bounds are beyond what f32 resolves,
+    in its denormal range (1e-42), all 0 or the smallest denormal (1e-46) or beyond FLT_MAX (1e39):
+    the device's __double2float_rd / ru against the exact refit's nextafter.  The update carries the
+    mesh from the control into the regime and back."""
+    import torch
+    base, _ = _pair(257)
+    nb = _normals(base)
+    there = M.mapped(base, *regime)
+    fresh = DeviceScene(_random_scene(there).spec(), 0, **FLAG_SETS[flags])
+    check_refit(fresh, [(there, nb)])
+    ds = DeviceScene(_random_scene(base).spec(), 0, **FLAG_SETS[flags])
+    before = check_refit(ds, [(base, nb)])
+    home = {key: ds.info()[key] for key in ("extent", "nan_free")}
+    ds.update_mesh(0, there, nb)
+    check_refit(ds, [(there, nb)], before)
+    for key in ("extent", "nan_free"):
+        assert ds.info()[key] == fresh.info()[key], key
+    tn = torch.from_numpy(nb).cuda()
+    for v in (base, there, base):
+        tv = torch.from_numpy(np.ascontiguousarray(v)).cuda()
+        ds.update_mesh_device(0, tv.data_ptr(), tn.data_ptr())
+        check_refit(ds, [(v, nb)], before)
+    assert {key: ds.info()[key] for key in home} == home
 
 
 @pytest.mark.parametrize("flags", ["default", "device_bvh", "device_sah"])

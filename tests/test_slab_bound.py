@@ -84,7 +84,7 @@ def f32_slab(b32, o, d, extent, rcp_rng=None, const_margin=False):
         # round_away_f32: (float)t times 1 + 2^-22, rounded (at least t)
         E2 = F32(F32(e2) * F32(1.0 + 2.0 ** -22)) if e2 < 1e30 else F32(np.inf)
         assert float(E2) >= e2
-        assert float(E2) >= 2.0 * float(e), (float(E2), float(e))
+        assert not float(E2) < 2.0 * float(e), (float(E2), float(e))  # (e is NaN where E2 = inf and a slab value is)
         dd = F32(lo - hi)
         if dd < -E2:
             return 1
@@ -134,3 +134,48 @@ def test_f32_pretest_never_contradicts_the_exact_test(rcp, const_margin):
             decided += 1
             assert bool(r) == exact, (b, o, d)
     assert decided > 0.8 * (decided + undecided)  # the pre-test decides most cases
+
+
+# ------------------------------------------------------------------- the scene at many magnitudes
+def _regime_cases():
+    import magnitude_scenes as M
+    return [pytest.param(r, id=i) for r, i in zip(M.REGIMES, M.REGIME_IDS)]
+
+
+@pytest.mark.parametrize("regime", _regime_cases())
+def test_f32_pretest_at_every_magnitude(regime):
+    """tests/magnitude_scenes.py's leaf boxes under x -> S x + T, with the kernel's per-ray E and its
+    `ek < 1e30` rule (else E = inf: every test is the f64 one): random rays from inside and from the
+    camera against random leaf boxes, and rays aimed at leaf-box corners nudged by -3 .. 3 ulp against
+    the box they are aimed at -- the only ones that sit on the margin (about three in four have an
+    f64 interval of relative width <= 1e-9; random rays give none).  Either f32 neighbour of each
+    reciprocal.  No f32 verdict may contradict the f64 division test."""
+    import magnitude_scenes as M
+    S, T = regime
+    boxes = M.leaf_boxes(S, T)
+    extent = M.scene_extent(S, T)
+    g = np.random.default_rng(17)
+    oc, dc = M.camera_rays(S, T, 400, 21)
+    oi, di = M.inside_rays(S, T, 400, 22)
+    ot, dt, aimed = M.corner_rays(boxes, S, T, 1200, 23)
+    o = np.concatenate([oc, oi, ot])
+    d = np.concatenate([dc, di, dt])
+    which = np.concatenate([g.integers(len(boxes), size=800), aimed])
+    tie, _ = M.near_ties(boxes[which], o, d)
+    # (at T = 2^24 + 1 one ulp of a coordinate is 7e-10 of the ray parameter: only the far origins tie)
+    assert tie[800:].sum() > (250 if T > 1e7 else 600) and not tie[:800].any()
+    rcp_rng = np.random.default_rng(29)
+    verdicts = np.empty(len(o), dtype=int)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        for k in range(len(o)):
+            b = boxes[which[k]]
+            r = verdicts[k] = f32_slab(outward(b), o[k], d[k], extent, rcp_rng, const_margin=True)
+            if r != 2:
+                assert bool(r) == f64_slab(b, o[k], d[k]), (k, b, o[k], d[k])
+    maybe, maybe_random = int((verdicts == 2).sum()), int((verdicts[:800] == 2).sum())
+    if regime in ((1.0, 0.0), (1e6, 0.0)):
+        assert maybe_random < 80                 # the margin is relative: the control decides, at any scale
+    if regime in ((1.0, 2.0 ** 24 + 1.0), (1e-6, 0.0), (1e36, 0.0)):
+        assert maybe == len(o)                   # f32 cannot resolve the boxes / the `+ 1` dominates / E = inf
+    if regime == (3e34, 0.0):
+        assert 0 < maybe_random < 800            # E finite or infinite per ray, by max |1/d|

@@ -604,6 +604,25 @@ __device__ __forceinline__ double sphere_distance(const Prim& s, const RayPre& p
 // the f64 evaluation errs by O(1e-16 (|o|^2 + |c|^2 + |oc|^2)) and this f32 estimate of
 // dist^2 - r^2 by < 2e-6 |oc|^2 (|d| = 1 +- 1e-16; conversions, products and sums each 6e-8
 // relative), so the margin 1e-4 |oc|^2 + 1e-12 (|o|^2 + |c|^2) covers both.  NaN: not missed.
+// Those relative bounds hold for f32 results in the normal range only.  A product that falls below
+// FLT_MIN = 2^-126 is rounded to a multiple of 2^-149 where denormals are kept (these code objects)
+// and to 0 where they are flushed: an absolute error below 2^-149, or 2^-126 flushed, in each of
+// the five products that are squares of the scene's scale (the three of oc2, t * t, r * r; those
+// of t itself only matter below |oc| = 2^-126, where oc2 is 0), none in the sums (an f32 sum or
+// difference that lands in the denormal range is exact), and as much again in each of the two
+// products of the right-hand side, which only ever lose (1e-12 (|o|^2 + |c|^2) can vanish whole,
+// and is then below 2^-126 itself).  The f64 evaluation's error, 1e-16 times such squares, is far
+// below either.  So at a scene scale of 1e-21 the margin 1e-4 |oc|^2 ~ 1e-46 was less than one
+// denormal step 1.4e-45 of the squares it was meant to cover, and real hits up to a tenth of the
+// radius inside the limb were skipped.  The absolute term 2^-120 in the right-hand side bounds all of
+// it, denormals kept (7 * 2^-149) or flushed (7 * 2^-126 < 2^-123): "missed" now needs the f32
+// dist^2 - r^2 > 2^-120, i.e. squares in the normal range with six bits to spare, where the
+// relative bounds above hold.  Below |oc| = 2^-60 (8.7e-19) the pre-test never rules a sphere out
+// (every sphere gets the f64 test: slower, never wrong); above |oc| ~ 1e-12 the term is below half
+// an ulp of the relative margin and the verdicts are the old ones; in between a few more grazing
+// rays take the f64 test, which decides as before.  The f32 sums overflow from
+// |oc| ~ 1.8e19 up: inf > inf is false and inf - inf is NaN, both "not missed".
+// tests/test_sphere_bound.py emulates the f32 arithmetic over scene scales 1e-23 .. 1e20.
 // the lanes (of the active ones) for which the pre-test cannot rule the sphere out, as one v_cmp:
 // !(lhs > rhs) is "unordered or less-equal"
 __device__ __forceinline__ uint64_t sphere_maybe32_lanes(const Prim& s, const RayPre& p) {
@@ -615,7 +634,7 @@ __device__ __forceinline__ uint64_t sphere_maybe32_lanes(const Prim& s, const Ra
     const float po = (float)p.o.x * (float)p.o.x + (float)p.o.y * (float)p.o.y + (float)p.o.z * (float)p.o.z;
     const float pc = (float)s.vec[0] * (float)s.vec[0] + (float)s.vec[1] * (float)s.vec[1] +
                      (float)s.vec[2] * (float)s.vec[2];
-    return __builtin_amdgcn_fcmpf((oc2 - t * t) - r * r, 1e-4f * oc2 + 1e-12f * (po + pc), 13 /* ule */);
+    return __builtin_amdgcn_fcmpf((oc2 - t * t) - r * r, (1e-4f * oc2 + 1e-12f * (po + pc)) + 0x1p-120f, 13 /* ule */);
 }
 
 // Plane::intersect (plane.rs:49-75): t or -1 (t == 0 is a hit).  NaN t (ray inside the plane)

@@ -89,14 +89,15 @@ __global__ __launch_bounds__(256) void integrate_kernel(IntegrateArgs A) {
                 go = true;
             }
         } else if (!best.kind) {
-            finish(lambda, Acc + T * sky_intensity(wo_y, lambda, &S.materials[S.sky_row]));  // simple_random_integrator.rs:43-46
+            // simple_random_integrator.rs:43-46; below a cut level (kPathCut) the sky term is discarded too
+            finish(lambda, (flags & kPathCut) ? Acc : Acc + T * sky_intensity(wo_y, lambda, &S.materials[S.sky_row]));
         } else {
             depth += 1;
             if (depth == kRecursionLimit) {  // integrate(.., 0) returns {0, 0}: lambda becomes 0
                 flags |= 2;
                 // the innermost photon's intensity 0 times the lambda-0 throughput: + 0 when finite,
                 // NaN when a level's pdf * |cos| was (the reference's 0 * NaN)
-                finish(0.0, Acc0 + T0 * 0.0);
+                finish(0.0, (flags & kPathCut) ? Acc0 : Acc0 + T0 * 0.0);
             } else {
                 go = true;
             }
@@ -206,9 +207,10 @@ __global__ __launch_bounds__(256) void integrate_kernel(IntegrateArgs A) {
                 const double c_l = material_intensity(mat, lambda);
                 const double c_0 = material_intensity(mat, 0.0);
                 double a, a0, bterm;
+                bool cut = false;  // this level's bsdf returns the constant 0 whatever comes from below
                 if (kind == 1) {  // reflective_material.rs:17-39
                     if (w_i.z <= 0.0 || w_o.z <= 0.0) {
-                        a = 0.0; a0 = 0.0; bterm = 0.0;
+                        a = 0.0; a0 = 0.0; bterm = 0.0; cut = true;
                     } else {
                         const V3 refl = mk(-w_o.x, -w_o.y, w_o.z);
                         double cth = dot(w_i, refl);
@@ -222,7 +224,7 @@ __global__ __launch_bounds__(256) void integrate_kernel(IntegrateArgs A) {
                     }
                 } else if (kind == 2) {  // phong_material.rs:17-36: diffuse + specular lobe
                     if (w_i.z < 0.0 || w_o.z < 0.0) {
-                        a = 0.0; a0 = 0.0; bterm = 0.0;
+                        a = 0.0; a0 = 0.0; bterm = 0.0; cut = true;
                     } else {
                         const V3 refl = mk(-w_i.x, -w_i.y, w_i.z);
                         a = ((pdf * cosf) * c_l) * mat->diffuse;
@@ -238,10 +240,14 @@ __global__ __launch_bounds__(256) void integrate_kernel(IntegrateArgs A) {
                     a0 = ((pdf * cosf) * c_0) * mat->diffuse;
                     bterm = 0.0;
                 }
-                Acc = Acc + T * bterm;
-                T = T * a;
-                Acc0 = Acc0 + T0 * bterm;
-                T0 = T0 * a0;
+                // (render_kernel's shade(): levels below a cut one are traced and change nothing)
+                if (!(flags & kPathCut)) {
+                    Acc = Acc + T * bterm;
+                    T = T * a;
+                    Acc0 = Acc0 + T0 * bterm;
+                    T0 = T0 * a0;
+                }
+                if (cut) flags |= kPathCut;
                 wo_y = wo_world.y;  // the sky term reads the un-normalised direction's y
             }
             // Ray::new(location, w_o).bias(1e-7): normalise, step, normalise again (mod.rs:41-61)
@@ -253,7 +259,7 @@ __global__ __launch_bounds__(256) void integrate_kernel(IntegrateArgs A) {
         if (fin) {
             // the caller reads them: plain 16-B and 8-B stores
             reinterpret_cast<vri_d2*>(A.photons)[i] = vri_d2{fin_wl, fin_I};
-            if (A.info) reinterpret_cast<vri_i2*>(A.info)[i] = vri_i2{bounces, flags};
+            if (A.info) reinterpret_cast<vri_i2*>(A.info)[i] = vri_i2{bounces, flags & ~kPathCut};
             live = false;
             i += stride;
         }

@@ -10,6 +10,9 @@
 namespace vr {
 
 constexpr int kRecursionLimit = 128;       // camera.rs:69
+// A path's internal flag beside the record's 1 (hit), 2 (limit), 4 (basis error): a level above has
+// returned the constant 0, so nothing traced from here on reaches the photon (never stored)
+constexpr int kPathCut = 8;
 constexpr int kMaxSpectrumSamples = 64;
 constexpr double kBounceBias = 0.0000001;  // simple_random_integrator.rs:42
 // VR_LAUNCH_DEFER_TIMES launches a stream may hold before vr_collect_launch_times (3 HIP events each)

@@ -628,7 +628,7 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
             rec->xyz[1] = c.y * Is;
             rec->xyz[2] = c.z * Is;
             rec->bounces = bounces;
-            rec->flags = flags;
+            rec->flags = flags & ~kPathCut;
         }
         if (COUNT) samples_done++;
         ++s_idx;
@@ -749,9 +749,10 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
         const double c_l = material_intensity(mat, lambda);
         const double c_0 = DARK0 ? 0.0 : material_intensity(mat, 0.0);
         double a, a0, bterm;
+        bool cut = false;  // this level's bsdf returns the constant 0 whatever comes from below
         if (kind == 1) {  // reflective_material.rs:17-39
             if (w_i.z <= 0.0 || w_o.z <= 0.0) {
-                a = 0.0; a0 = 0.0; bterm = 0.0;
+                a = 0.0; a0 = 0.0; bterm = 0.0; cut = true;
             } else {
                 const V3 refl = mk(-w_o.x, -w_o.y, w_o.z);
                 double cth = dot(w_i, refl);
@@ -765,7 +766,7 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
             }
         } else if (MATS == 3 && kind == 2) {  // phong_material.rs:17-36: diffuse + specular lobe
             if (w_i.z < 0.0 || w_o.z < 0.0) {
-                a = 0.0; a0 = 0.0; bterm = 0.0;
+                a = 0.0; a0 = 0.0; bterm = 0.0; cut = true;
             } else {
                 const V3 refl = mk(-w_i.x, -w_i.y, w_i.z);
                 a = ((pdf * cosf) * c_l) * mat->diffuse;
@@ -782,12 +783,22 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
             bterm = 0.0;
         }
         if (depth == 0) b0 = bterm;
-        Acc = Acc + T * bterm;
-        T = T * a;
-        if (!DARK0) {
-            Acc0 = Acc0 + T0 * bterm;
-            T0 = T0 * a0;
+        // A cut level (a mirror or Phong surface met from behind) returns intensity 0 without reading
+        // what comes from below (reflective_material.rs:20-24, phong_material.rs:19-21): the recursion
+        // still traces the levels below it -- they count bounces, reach the limit, raise the basis
+        // error -- but a NaN there (a bounce ray that re-hits its own surface at distance 0, as every
+        // trapped path of a scene scaled by 1e20 does) is discarded, where T * a would turn the
+        // forward product 0 * NaN.  From the cut on (kPathCut in `flags`, cleared per path and masked
+        // out of the record) the products are frozen and the path's end adds nothing.
+        if (!(flags & kPathCut)) {
+            Acc = Acc + T * bterm;
+            T = T * a;
+            if (!DARK0) {
+                Acc0 = Acc0 + T0 * bterm;
+                T0 = T0 * a0;
+            }
         }
+        if (cut) flags |= kPathCut;
         // A path whose every continuation yields intensity 0 stops here -- only in scenes the host
         // proved NaN-free (A.early_stop: every mesh triangle's shading basis is finite for any
         // barycentric point, no Phong / dielectric): the reference keeps recursing and returns
@@ -1219,7 +1230,8 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                         go = true;
                     }
                 } else if (!best.kind) {
-                    finish(lambda, Acc + T * sky_intensity(wo_y, lambda, &S.materials[S.sky_row]));  // simple_random_integrator.rs:43-46
+                    // simple_random_integrator.rs:43-46; below a cut level the sky term is discarded too
+                    finish(lambda, (flags & kPathCut) ? Acc : Acc + T * sky_intensity(wo_y, lambda, &S.materials[S.sky_row]));
                 } else {
                     depth += 1;
                     if (depth == kRecursionLimit) {  // integrate(.., 0) returns {0, 0}: lambda becomes 0
@@ -1227,7 +1239,7 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                         // the innermost photon's intensity 0 times the lambda-0 throughput: + 0
                         // when finite, NaN when a level's pdf * |cos| was (the reference's 0 * NaN);
                         // DARK0 scenes are NaN-free (host), where every lambda-0 level is 0 * I + b
-                        finish(0.0, DARK0 ? b0 : Acc0 + T0 * 0.0);
+                        finish(0.0, DARK0 ? b0 : (flags & kPathCut) ? Acc0 : Acc0 + T0 * 0.0);
                     } else {
                         go = true;
                     }
