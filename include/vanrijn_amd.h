@@ -286,7 +286,8 @@ int vr_scene_bvh_roots(const vr_scene* scene, void* out);
 #define VR_HAS_SCENE_EDIT 1
 /* vr_scene_desc::camera_location.  A coordinate that is not finite: VR_ERROR_INVALID_ARGUMENT.
  * vr_scene_info::extent and the cull margins follow.  The camera is a launch argument, not in HBM:
- * this call makes no device call at all, on any scene. */
+ * this call makes no device call at all, on any scene.  It changes the location only: the basis and
+ * the film distance of the scene's pose (vr_scene_set_camera_pose below) stay. */
 int vr_scene_set_camera(vr_scene* scene, vr_vec3 location);
 /* Entries first .. first + count - 1 of vr_scene_desc::primitives; kind, material, vector and scalar may
  * all change.  Every row a primitive list made from such an entry is rebuilt as vr_scene_create builds it
@@ -344,6 +345,54 @@ int vr_scene_transform_mesh(vr_scene* scene, uint32_t mesh, const double matrix[
 int vr_scene_primitives(const vr_scene* scene, void* out, uint32_t* count);
 int vr_scene_materials(const vr_scene* scene, void* out, uint32_t* count);
 int vr_scene_get_camera(const vr_scene* scene, vr_vec3* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Camera pose: where the camera looks and how wide.  The reference's ImageSampler (camera.rs:24-66)
+ * looks down +z from camera_location with the film one unit away; a pose turns and zooms it.  Added
+ * under ABI 10 (VR_HAS_CAMERA_POSE).
+ *
+ * The ray rule.  x and y are the reference's film coordinates of the sample (the film is width / height
+ * by 1 when width > height, else 1 by width / height: the image's shorter side spans a film length of 1;
+ * the jitter is draws 0 and 1 of the pixel-sample stream, x first).  For each component c, in f64, without contraction, in this order:
+ *     d_c = (x * right_c + y * up_c) + film_distance * forward_c
+ * and the ray is Ray::new(location, d): origin `location`, direction d * (1 / |d|).
+ * The default pose -- right (1,0,0), up (0,1,0), forward (0,0,1), film_distance 1.0, which every scene
+ * has from vr_scene_create on -- gives the reference's rays bit for bit.
+ * Field of view: across the image's shorter side, whose film length is 1, it is
+ * 2 * atan(0.5 / film_distance) (53.13 degrees at 1.0); across the other side, of film length
+ * width / height, 2 * atan(0.5 * (width / height) / film_distance).
+ * Every entry point that forms camera rays reads the scene's pose: vr_render_tile*,
+ * vr_partial_render_scene, vr_film_*, vr_render_samples, vr_camera_rays_device and the block cull,
+ * which stays conservative under any admitted pose.  No entry point takes a new parameter.
+ * --------------------------------------------------------------------------------------------- */
+#define VR_HAS_CAMERA_POSE 1
+typedef struct vr_camera_pose {
+    vr_vec3 location, right, up, forward;
+    double film_distance;
+} vr_camera_pose;
+/* A scene edit: the contract above applies word for word (blocking; not thread-safe against other calls
+ * on the scene; errors before anything is modified; works on VR_SCENE_HOST_ONLY scenes).  Like
+ * vr_scene_set_camera it makes no device call: the pose is a launch argument.  vr_scene_info::extent and
+ * the cull margins follow the location.  The axes are stored and used as given; either handedness is
+ * allowed (a right-handed basis renders the mirrored view).
+ * VR_ERROR_INVALID_ARGUMENT: a null argument; an entry that is not finite; two axes with |a . b| > 1e-9;
+ * an axis with | |a|^2 - 1 | > 1e-9; film_distance outside [1e-3, 1e3]. */
+int vr_scene_set_camera_pose(vr_scene* scene, const vr_camera_pose* pose);
+int vr_scene_get_camera_pose(const vr_scene* scene, vr_camera_pose* out);
+/* Host helper, no scene: the left-handed basis (x right, y up, z forward, as the reference's) of a camera
+ * at `eye` looking at `target`, in this fixed arithmetic (normalize as the rule's; cross as vec3.rs:84-89):
+ *     forward = normalize(target - eye);  right = normalize(cross(up_hint, forward));  up = cross(forward, right)
+ * eye 0, target (0,0,1), up_hint (0,1,0), film_distance 1.0 returns the default pose exactly.
+ * VR_ERROR_INVALID_ARGUMENT: a null out; an input that is not finite; eye == target; up_hint parallel to
+ * the view direction (|cross(up_hint, forward)|^2 <= 1e-24 |up_hint|^2); film_distance outside [1e-3, 1e3];
+ * inputs so large or small that the result would not pass vr_scene_set_camera_pose.  *out is written on
+ * VR_OK only. */
+int vr_camera_look_at(vr_vec3 eye, vr_vec3 target, vr_vec3 up_hint, double film_distance, vr_camera_pose* out);
+/* The ray rule on the host, from the same inline function the kernels compile: the camera ray of pixel
+ * (row, column) of a width x height image with jitter (ux, uy).  The pose is used as given (not
+ * validated).  VR_ERROR_INVALID_ARGUMENT: a null argument, an empty image, a pixel outside it. */
+int vr_camera_ray(const vr_camera_pose* pose, uint64_t width, uint64_t height, uint64_t row, uint64_t column,
+                  double ux, double uy, double origin[3], double direction[3]);
 
 /* util::Tile (src/util/tile_iterator.rs:1-7): half-open row/column ranges of the full image. */
 typedef struct vr_tile {

@@ -41,6 +41,10 @@ class Vec3(C.Structure):
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("z", C.c_double)]
 
 
+class CameraPose(C.Structure):
+    _fields_ = [("location", Vec3), ("right", Vec3), ("up", Vec3), ("forward", Vec3), ("film_distance", C.c_double)]
+
+
 class Spectrum(C.Structure):
     _fields_ = [("shortest_wavelength", C.c_double), ("longest_wavelength", C.c_double),
                 ("sample_count", C.c_uint32), ("samples", C.POINTER(C.c_double))]
@@ -182,6 +186,10 @@ SIGNATURES = {
     "vr_scene_primitives": (C.c_int, [_p, _p, C.POINTER(C.c_uint32)]),
     "vr_scene_materials": (C.c_int, [_p, _p, C.POINTER(C.c_uint32)]),
     "vr_scene_get_camera": (C.c_int, [_p, C.POINTER(Vec3)]),
+    "vr_scene_set_camera_pose": (C.c_int, [_p, C.POINTER(CameraPose)]),
+    "vr_scene_get_camera_pose": (C.c_int, [_p, C.POINTER(CameraPose)]),
+    "vr_camera_look_at": (C.c_int, [Vec3, Vec3, Vec3, _d, C.POINTER(CameraPose)]),
+    "vr_camera_ray": (C.c_int, [C.POINTER(CameraPose), _u64, _u64, _u64, _u64, _d, _d, _p, _p]),
     "vr_partial_render_scene": (C.c_int, [_p, TileC, _u64, _u64, C.POINTER(AccumulationBufferC)]),
     "vr_render_tile": (C.c_int, [_p, C.POINTER(RenderParams), C.POINTER(AccumulationBufferC)]),
     "vr_render_tile_device": (C.c_int, [_p, C.POINTER(RenderParams), _p, _p, _u32, C.POINTER(LaunchStats)]),

@@ -248,15 +248,15 @@ vr::RenderArgs make_args(const vr_scene* s, const vr_render_params* p, double* s
     a.item_order = io ? (uint32_t)(atoi(io) != 0) : (block_major ? 1u : 0u);
     const char* pr = tuning_env("VR_PHASE_A_REPS");  // tuning hook
     a.phase_a_reps = pr ? (uint32_t)std::max(1, atoi(pr)) : 2u;
+    // same f64 operations as the reference's ImageSampler::new / film_to_world
+    vr::camera::film_constants(a.width, a.height, a.film);
     {
-        // same f64 operations as the reference's ImageSampler::new / film_to_world
-        const double fw = (double)a.width, fh = (double)a.height;
-        const double film_w = fw > fh ? fw / fh : 1.0;
-        const double film_h = fw > fh ? 1.0 : fw / fh;
-        a.film[0] = film_w * (1.0 / fw);
-        a.film[1] = film_w * 0.5;
-        a.film[2] = film_h * (1.0 / fh);
-        a.film[3] = film_h * 0.5;
+        // by value: an axis entry of -0.0 is a default entry too (its products are +-0 as well)
+        const vr::PoseArgs& d = s->pose;
+        const double pose[10] = {d.right[0], d.right[1], d.right[2], d.up[0], d.up[1],
+                                 d.up[2], d.forward[0], d.forward[1], d.forward[2], d.film_distance};
+        const double standard[10] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 1.0};
+        a.posed = std::equal(pose, pose + 10, standard) ? 0u : 1u;
     }
     {
         const uint64_t bw = (a.tile_width + 7) / 8, bh = (a.tile_height + 7) / 8;
@@ -411,7 +411,7 @@ int enqueue_passes(vr_scene* s, CallCtx* c, const vr_render_params* p, double* s
         if (rc) return rc;
         if (nb >= (1ull << 32)) return fail(VR_ERROR_UNSUPPORTED, "too many pixel blocks in one tile (2^32)");
         vr::RenderArgs a = make_args(s, p, state);
-        int lc = vr::launch_block_cull(a, (uint8_t*)c->mask, st);
+        int lc = vr::launch_block_cull(a, s->pose, (uint8_t*)c->mask, st);
         uint32_t* lst = (uint32_t*)((char*)c->mask + list_off);
         const char* bm = tuning_env("VR_BLOCK_MORTON");  // tuning hook: live blocks in Z-order
         const bool morton = bm ? atoi(bm) != 0 : (s->mats & 2) == 0;  // with block-major items (make_args)
@@ -494,7 +494,7 @@ int enqueue_passes(vr_scene* s, CallCtx* c, const vr_render_params* p, double* s
                        (lc.s16 ? VR_VARIANT_STACK16 : 0u);
         // the COOP instantiations (2 waves per SIMD) keep 3 workgroups per CU (coop_grid_per_cu)
         const int per_cu = lc.coop ? coop_grid_per_cu() : grid_per_cu();
-        int lr = vr::launch_render(a, lc, std::max(1, s->cu_count) * per_cu, st, mid);
+        int lr = vr::launch_render(a, s->pose, lc, std::max(1, s->cu_count) * per_cu, st, mid);
         if (lr) return launch_status(lr);
         if (timing) {
             hipEvent_t end = timing->add();

@@ -73,6 +73,8 @@ int32_t shape_wide(uint64_t n, int32_t node_base, int32_t tri_base, std::vector<
 #include <unordered_map>
 #include <utility>
 
+#include "vr_camera.h"
+
 #define VR_HIP(call)                                                                               \
     do {                                                                                           \
         hipError_t e_ = (call);                                                                    \
@@ -85,6 +87,8 @@ struct vr_scene {
     int device = -1;
     bool host_only = false;
     double camera[3];
+    // the camera pose beside the location (vr_scene_set_camera_pose): the default is the reference's camera
+    vr::PoseArgs pose = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}, 1.0};
     double extent = 0.0;
     std::vector<vr::Material> materials;
     std::vector<vr::Prim> prims;

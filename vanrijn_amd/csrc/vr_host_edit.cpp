@@ -328,6 +328,89 @@ int vr_scene_set_camera(vr_scene* s, vr_vec3 location) {
     return VR_OK;
 }
 
+namespace {
+
+bool finite3(vr_vec3 v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); }
+double dot3(vr_vec3 a, vr_vec3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+vr_vec3 cross3(vr_vec3 a, vr_vec3 b) {  // vec3.rs:84-89
+    return vr_vec3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+vr_vec3 normalize3(vr_vec3 a) {
+    const vr::camera::Vec n = vr::camera::normalize(vr::camera::Vec{a.x, a.y, a.z});
+    return vr_vec3{n.x, n.y, n.z};
+}
+bool film_distance_ok(double f) { return f >= 1e-3 && f <= 1e3; }  // false for a NaN
+// what vr_scene_set_camera_pose admits (the block cull's margins are sized for these bounds)
+const char* pose_error(const vr_camera_pose& p) {
+    if (!finite3(p.location) || !finite3(p.right) || !finite3(p.up) || !finite3(p.forward) ||
+        !std::isfinite(p.film_distance))
+        return "camera pose: an entry is not finite";
+    if (!film_distance_ok(p.film_distance)) return "camera pose: film_distance outside [1e-3, 1e3]";
+    const vr_vec3 axes[3] = {p.right, p.up, p.forward};
+    for (int i = 0; i < 3; ++i) {
+        if (std::fabs(dot3(axes[i], axes[i]) - 1.0) > 1e-9) return "camera pose: an axis is not of unit length (1e-9)";
+        if (std::fabs(dot3(axes[i], axes[(i + 1) % 3])) > 1e-9) return "camera pose: two axes are not orthogonal (1e-9)";
+    }
+    return nullptr;
+}
+
+}  // namespace
+
+int vr_scene_set_camera_pose(vr_scene* s, const vr_camera_pose* pose) {
+    if (!s || !pose) return fail(VR_ERROR_INVALID_ARGUMENT, "null scene or pose");
+    if (const char* why = pose_error(*pose)) return fail(VR_ERROR_INVALID_ARGUMENT, why);
+    vr::PoseArgs& d = s->pose;
+    const vr_vec3 axes[3] = {pose->right, pose->up, pose->forward};
+    double* dst[3] = {d.right, d.up, d.forward};
+    for (int i = 0; i < 3; ++i) {  // stored and used as given
+        dst[i][0] = axes[i].x;
+        dst[i][1] = axes[i].y;
+        dst[i][2] = axes[i].z;
+    }
+    d.film_distance = pose->film_distance;
+    return vr_scene_set_camera(s, pose->location);  // cannot fail: the location is finite
+}
+
+int vr_camera_look_at(vr_vec3 eye, vr_vec3 target, vr_vec3 up_hint, double film_distance, vr_camera_pose* out) {
+    if (!out) return fail(VR_ERROR_INVALID_ARGUMENT, "null pose");
+    if (!finite3(eye) || !finite3(target) || !finite3(up_hint) || !std::isfinite(film_distance))
+        return fail(VR_ERROR_INVALID_ARGUMENT, "look_at: an argument is not finite");
+    if (!film_distance_ok(film_distance)) return fail(VR_ERROR_INVALID_ARGUMENT, "look_at: film_distance outside [1e-3, 1e3]");
+    const vr_vec3 view{target.x - eye.x, target.y - eye.y, target.z - eye.z};
+    if (!finite3(view)) return fail(VR_ERROR_INVALID_ARGUMENT, "look_at: target - eye is not finite");
+    if (view.x == 0.0 && view.y == 0.0 && view.z == 0.0) return fail(VR_ERROR_INVALID_ARGUMENT, "look_at: eye == target");
+    const vr_vec3 forward = normalize3(view);
+    const vr_vec3 side = cross3(up_hint, forward);
+    if (!finite3(forward) || !(dot3(side, side) > 1e-24 * dot3(up_hint, up_hint)))
+        return fail(VR_ERROR_INVALID_ARGUMENT, "look_at: up_hint is parallel to the view direction");
+    const vr_vec3 right = normalize3(side);
+    const vr_vec3 up = cross3(forward, right);
+    vr_camera_pose p{eye, right, up, forward, film_distance};
+    if (pose_error(p)) return fail(VR_ERROR_INVALID_ARGUMENT, "look_at: the arguments' magnitudes leave no orthonormal basis");
+    *out = p;
+    return VR_OK;
+}
+
+int vr_camera_ray(const vr_camera_pose* pose, uint64_t width, uint64_t height, uint64_t row, uint64_t column, double ux,
+                  double uy, double origin[3], double direction[3]) {
+    if (!pose || !origin || !direction) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
+    if (width == 0 || height == 0 || row >= height || column >= width)
+        return fail(VR_ERROR_INVALID_ARGUMENT, "camera ray: the pixel is outside the image");
+    double film[4];
+    vr::camera::film_constants(width, height, film);
+    const double r[3] = {pose->right.x, pose->right.y, pose->right.z}, u[3] = {pose->up.x, pose->up.y, pose->up.z};
+    const double f[3] = {pose->forward.x, pose->forward.y, pose->forward.z};
+    const vr::camera::Vec d = vr::camera::ray_direction(r, u, f, pose->film_distance, vr::camera::film_x(film, column, ux),
+                                                        vr::camera::film_y(film, height, row, uy));
+    origin[0] = pose->location.x;
+    origin[1] = pose->location.y;
+    origin[2] = pose->location.z;
+    direction[0] = d.x;
+    direction[1] = d.y;
+    direction[2] = d.z;
+    return VR_OK;
+}
+
 int vr_scene_update_primitives(vr_scene* s, uint32_t first, uint32_t count, const vr_primitive_desc* prims) {
     if (!s) return fail(VR_ERROR_INVALID_ARGUMENT, "null scene");
     if ((uint64_t)first + count > s->prim_rows.size())

@@ -257,6 +257,7 @@ int vr_camera_rays_device(const vr_scene* s, const vr_render_params* p, double* 
     const vr::RenderArgs r = make_args(s, p, nullptr);
     vr::CameraRaysArgs a{};
     for (int k = 0; k < 3; ++k) a.camera[k] = s->dev.camera[k];
+    a.pose = s->pose;
     a.start_column = r.start_column;
     a.start_row = r.start_row;
     a.tile_width = r.tile_width;

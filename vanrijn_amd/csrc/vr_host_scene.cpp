@@ -605,6 +605,17 @@ int vr_scene_get_camera(const vr_scene* s, vr_vec3* out) {
     return VR_OK;
 }
 
+int vr_scene_get_camera_pose(const vr_scene* s, vr_camera_pose* out) {
+    if (!s || !out) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
+    const vr::PoseArgs& d = s->pose;
+    out->location = vr_vec3{s->camera[0], s->camera[1], s->camera[2]};
+    out->right = vr_vec3{d.right[0], d.right[1], d.right[2]};
+    out->up = vr_vec3{d.up[0], d.up[1], d.up[2]};
+    out->forward = vr_vec3{d.forward[0], d.forward[1], d.forward[2]};
+    out->film_distance = d.film_distance;
+    return VR_OK;
+}
+
 int vr_scene_wide_nodes(const vr_scene* s, void* out) {
     if (!s || !out) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
     return dump_rows(s, host_copies_current(s), s->dev.nodes4, s->nodes4.data(), s->wide_count * sizeof(vr::Node4), out);

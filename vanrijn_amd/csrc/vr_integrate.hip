@@ -20,6 +20,7 @@
 #include "../../include/vanrijn_amd.h"
 #include "vr_layout.h"
 #include "vr_exp_table.h"
+#include "vr_camera.h"
 
 #include "vr_device.h"
 #include "vr_walk4.h"
@@ -267,7 +268,8 @@ __global__ __launch_bounds__(256) void integrate_kernel(IntegrateArgs A) {
 }
 
 // ImageSampler::ray_for_pixel (camera.rs:24-66) for entry j = s * (tile pixels) + p: render_kernel's
-// camera step (the jitter is draws 0 and 1 of the (pixel, sample) stream, x before y)
+// camera step (the jitter is draws 0 and 1 of the (pixel, sample) stream, x before y) under the
+// scene's pose: vr_camera.h's rule
 __global__ __launch_bounds__(256) void camera_rays_kernel(CameraRaysArgs A) {
     const uint64_t npix = A.tile_width * A.tile_height;
     const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -280,9 +282,9 @@ __global__ __launch_bounds__(256) void camera_rays_kernel(CameraRaysArgs A) {
     rng.reset(mix64(A.seed_key ^ id));
     const double ux = rng.standard();
     const double uy = rng.standard();
-    const double x = ((double)col + ux) * A.film[0] - A.film[1];
-    const double y = ((double)(A.height - (row + 1)) + uy) * A.film[2] - A.film[3];
-    const V3 d = normalize(mk(x, y, 1.0));
+    const double x = camera::film_x(A.film, col, ux);
+    const double y = camera::film_y(A.film, A.height, row, uy);
+    const camera::Vec d = camera::ray_direction(A.pose.right, A.pose.up, A.pose.forward, A.pose.film_distance, x, y);
     A.origins[3 * j] = A.camera[0];
     A.origins[3 * j + 1] = A.camera[1];
     A.origins[3 * j + 2] = A.camera[2];

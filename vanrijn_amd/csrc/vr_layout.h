@@ -142,6 +142,15 @@ struct DeviceScene {
     const double* light_dirs;
 };
 
+// The camera pose (vr_camera.h: the ray rule): an orthonormal basis, used as given, and the film's
+// distance along `forward`; the default (1,0,0), (0,1,0), (0,0,1), 1 is the reference's camera.  The
+// render kernel and the block cull take it as their LAST kernel argument, so that every other argument
+// keeps its offset in the kernel-argument segment (DESIGN.md section 2 "Camera pose").
+struct PoseArgs {
+    double right[3], up[3], forward[3];
+    double film_distance;
+};
+
 struct RenderArgs {
     DeviceScene scene;
     uint64_t start_column, start_row, tile_width, tile_height;
@@ -212,7 +221,9 @@ struct RenderArgs {
     uint64_t probe_n;
     uint32_t* stage_tag;  // [pass sample][tile pixel], or nullptr
     uint32_t stage_gen;   // this pass's generation (never 0)
-    uint32_t pad_gen;
+    // 1: the scene's pose is not the default one and the camera step loads it (vr_render.hip
+    // load_pose_args); 0: the step forms normalize((x, y, 1)), which the rule gives for the default pose
+    uint32_t posed;
 };
 
 struct TraceArgs {
@@ -257,6 +268,7 @@ struct IntegrateArgs {
 // vr_integrate.hip: ImageSampler::ray_for_pixel for every (sample, pixel) of a tile, [s][p] order
 struct CameraRaysArgs {
     double camera[3];
+    PoseArgs pose;
     uint64_t start_column, start_row, tile_width, tile_height;
     uint64_t width, height;
     uint64_t seed_key, first_sample;
@@ -303,11 +315,11 @@ struct LaunchChoice {
     bool big;         // 64-bit node / triangle load offsets (vr_host.cpp needs_big_offsets)
     bool s16;         // 16-bit LDS stack entries (trees below 65,536 wide nodes; timed kernels only)
 };
-int launch_render(const RenderArgs& args, const LaunchChoice& choice, int grid_limit, void* stream,
+int launch_render(const RenderArgs& args, const PoseArgs& pose, const LaunchChoice& choice, int grid_limit, void* stream,
                   void* mid_event = nullptr);
 // vr_image.hip: records (from_state = 1, RenderArgs::state's layout) or XYZ colour (3 f64) -> sRGB8
 // the camera-frustum test of every 8x8 block of a launch's tile into mask (RenderArgs::block_mask)
-int launch_block_cull(const RenderArgs& args, uint8_t* mask, void* stream);
+int launch_block_cull(const RenderArgs& args, const PoseArgs& pose, uint8_t* mask, void* stream);
 // the live (unculled) blocks of `mask` (n blocks) in order into live[], their number into *count
 int launch_block_compact(const uint8_t* mask, uint32_t bw, uint32_t bh, bool morton, uint32_t* live, uint32_t* count,
                          void* stream);

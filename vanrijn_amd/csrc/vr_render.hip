@@ -33,6 +33,7 @@
 #include "rgb_spectrum_tables.h"
 #include "vr_layout.h"
 #include "vr_exp_table.h"
+#include "vr_camera.h"
 
 #include "vr_device.h"
 
@@ -175,6 +176,30 @@ __device__ void coop_prof_dump(unsigned long long* o, bool coop_on, unsigned lan
 }
 #endif
 
+// The camera pose of the launch: render_kernel's last argument, which the kernel never names.  The camera
+// step reads it from the kernel-argument segment as kargs() above reads the base pointers: ten scalar
+// loads per camera ray of a wave.  Read as an ordinary argument its 20 scalar registers stay live through
+// the whole kernel, on top of a register file that is full: measured, up to 98 more scalar spills and up
+// to 72 B more scratch per instantiation.  It comes last because every other argument then keeps its
+// offset: as a member of RenderArgs::scene it moved the scratch of most instantiations, the default
+// pose's included, by shifting what follows it (DESIGN.md section 2 "Camera pose").
+struct RenderKernargs {  // render_kernel's argument list as the segment holds it (every member 8-aligned)
+    RenderArgs args;
+    const Prim* prims;
+    const Material* materials;
+    const Bvh* bvhs;
+    PoseArgs pose;
+};
+__device__ __forceinline__ camera::Vec posed_direction(double x, double y) {
+    typedef __attribute__((address_space(4))) const RenderKernargs* Segment;
+    Segment k = (Segment)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    const double r[3] = {k->pose.right[0], k->pose.right[1], k->pose.right[2]};
+    const double u[3] = {k->pose.up[0], k->pose.up[1], k->pose.up[2]};
+    const double f[3] = {k->pose.forward[0], k->pose.forward[1], k->pose.forward[2]};
+    return camera::ray_direction(r, u, f, k->pose.film_distance, x, y);
+}
+
 // MATS: material kinds present (1 Lambertian, 2 reflective, 3 both); code for absent kinds is
 // compiled out, which keeps the reflective BSDF's acos/pow/exp off Lambertian-only scenes.
 // WHITTED: the WhittedIntegrator (whitted_integrator.rs:20-87) instead of SimpleRandomIntegrator.
@@ -189,14 +214,18 @@ __device__ void coop_prof_dump(unsigned long long* o, bool coop_on, unsigned lan
 // object) instead of shading, and no path state exists, so the register peak is traversal's alone.
 // S16: 16-bit LDS stack entries (trees below 65,536 wide nodes): half the stack's LDS, so more
 // workgroups fit a CU.
+// POSED: the camera step applies the scene's pose (RenderArgs::posed).  The default pose keeps its own
+// instantiations, whose code is what it was before poses existed: in a kernel whose registers are all
+// taken, a pose read in the shared code moved spills and scratch of a dozen instantiations whichever way
+// it was loaded (DESIGN.md section 2 "Camera pose").
 template <int STACK, bool COUNT, bool RECORD, bool DARK0, int MATS = 3, int MINW = 3, bool WHITTED = false,
-          bool COOP = false, bool BIG = false, bool TRACE = false, bool S16 = false>
+          bool COOP = false, bool BIG = false, bool TRACE = false, bool S16 = false, bool POSED = false>
 // The scene's small uniform tables (planes / spheres, materials, BVH roots) come in again as
 // restrict-qualified arguments: nothing the kernel stores can alias them, so their wave-uniform
 // reads compile to scalar loads (the scalar cache) instead of vector loads through L2.
 __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const Prim* __restrict__ g_prims,
                                                            const Material* __restrict__ g_materials,
-                                                           const Bvh* __restrict__ g_bvhs) {
+                                                           const Bvh* __restrict__ g_bvhs, PoseArgs) {
     typedef typename std::conditional<S16, uint16_t, uint32_t>::type StackT;
     __shared__ StackT st_node[STACK * 256];
     // leaf triangles met during traversal wait for a leaf round, in which every lane tests one: the
@@ -1352,13 +1381,18 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                 // film_w * (1 / w), film_w * 0.5, ... are per-launch constants (host: make_args)
                 const double ux = rng.standard();
                 const double uy = rng.standard();
-                const double x = ((double)col + ux) * A.film[0] - A.film[1];
-                const double y = ((double)(A.height - (row + 1)) + uy) * A.film[2] - A.film[3];
+                const double x = camera::film_x(A.film, col, ux);
+                const double y = camera::film_y(A.film, A.height, row, uy);
                 depth = -1;
                 bounces = 0;
                 flags = 0;
                 pre.o = mk(S.camera[0], S.camera[1], S.camera[2]);
-                pre.d = normalize(mk(x, y, 1.0));
+                if constexpr (POSED) {  // the scene's pose (vr_camera.h: the ray rule)
+                    const camera::Vec cd = posed_direction(x, y);
+                    pre.d = mk(cd.x, cd.y, cd.z);
+                } else {  // the default pose: what the rule gives for it, bit for bit (vr_camera.h)
+                    pre.d = normalize(mk(x, y, 1.0));
+                }
                 state = kRayReady;
             }
             if (state == kRayReady) {
@@ -1626,24 +1660,37 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
 // Camera-frustum test of the tile's 8x8 pixel blocks (one thread per block).  The camera rays of a
 // block start at the camera and pass through the film rectangle its pixels' sample squares cover
 // (camera.rs:24-66: x = (col + u) fw/w - fw/2, y = (h - row - 1 + v) fh/h - fh/2, u, v in [0, 1),
-// direction (x, y, 1) normalised).  A block is culled only when every such line provably misses
-// every object, with margins far beyond the f64 rounding of the reference's tests:
-//  * a plane (plane.rs:49-75): its t = num / dn is negative for every ray -- num and n . (x, y, 1)
-//    of opposite signs at all four corners of the rectangle (a linear function: its extremes),
-//    each by more than 1e-9 of its magnitude scale;
+// direction d(x, y) = x right + y up + film_distance forward normalised: vr_camera.h's rule, so
+// (x, y, 1) under the default pose).  d is affine in (x, y), so the block's directions are the
+// parallelogram spanned by d at the rectangle's four corners, in world space, where every test
+// below is made.  A block is culled only when every such line provably misses every object, with
+// margins far beyond the f64 rounding of the reference's tests:
+//  * a plane (plane.rs:49-75): its t = num / dn is negative for every ray -- num and n . d
+//    of opposite signs at all four corners of the rectangle (n . d is affine on the parallelogram:
+//    its extremes are at the corners), each by more than 1e-9 of its magnitude scale;
 //  * a BVH root box (a ray that misses the box misses every triangle in it) wholly in front of the
-//    camera: the bounding rectangle of its corners' film projections (x/z, y/z), widened by 1e-6,
-//    misses the block's film rectangle;
+//    camera: its corners p - location in camera coordinates (p . right, p . up, p . forward) =: (px,
+//    py, pz); the directions that reach the box have (x, y) / film_distance inside the bounding
+//    rectangle of the corners' (px / pz, py / pz), which, widened, misses the block's film
+//    rectangle divided by film_distance.  The dot products apply the basis' transpose where its
+//    inverse is meant.  vr_scene_set_camera_pose admits a basis B = [right up forward] with
+//    |B^T B - I| <= 1e-9 per entry, so with w = (x, y, film_distance) the computed triple is
+//    t (w + E w), |E w|_i <= 1e-9 (|x| + |y| + film_distance), and px / pz is off x / film_distance
+//    by at most 1e-9 s^2 (1 + 1e-9 s), s = 1 + (|x| + |y|) / film_distance: the rectangle is widened
+//    by 1e-6 s^2 with s from the computed bounds, a thousand times that and the f64 rounding of the
+//    dot products (the front test leaves |px|, |py| <= 1e6 pz, so 1e-9 s stays below 1e-2);
 //  * a sphere, or a root box through its bounding sphere: the camera is outside it and the angle
 //    between the sphere's centre and the axis of the block's cone of directions exceeds the cone's
-//    half-angle (attained at a corner) plus the sphere's angular radius plus 1e-6 rad.
+//    half-angle (attained at a corner) plus the sphere's angular radius plus 1e-6 rad.  A cone of
+//    half-angle below 90 degrees is convex, so holding the four corner directions it holds every
+//    positive combination of them: every direction of the block (a wider cone is not used).
 // Each sample of a culled block is then exactly the missed camera ray's photon {0, 0}, whatever
 // its random draws.
 __device__ __forceinline__ double vr_angle(V3 a, V3 b) {
     return atan2(sqrt(dot(cross(a, b), cross(a, b))), dot(a, b));
 }
 __global__ __launch_bounds__(256) void block_cull_kernel(RenderArgs A, const Prim* prims, const Bvh* bvhs,
-                                                         uint8_t* mask) {
+                                                         uint8_t* mask, PoseArgs pose) {
     const uint32_t bw = (uint32_t)((A.tile_width + 7) / 8), bh = (uint32_t)((A.tile_height + 7) / 8);
     const uint32_t b = blockIdx.x * 256 + threadIdx.x;
     if (b >= bw * bh) return;
@@ -1658,18 +1705,28 @@ __global__ __launch_bounds__(256) void block_cull_kernel(RenderArgs A, const Pri
     const double mx = 1e-9 * (fabs(xa) + fabs(xb) + 1.0), my = 1e-9 * (fabs(ya) + fabs(yb) + 1.0);
     const double xlo = fmin(xa, xb) - mx, xhi = fmax(xa, xb) + mx;
     const double ylo = fmin(ya, yb) - my, yhi = fmax(ya, yb) + my;
-    const V3 pc[4] = {mk(xlo, ylo, 1.0), mk(xhi, ylo, 1.0), mk(xlo, yhi, 1.0), mk(xhi, yhi, 1.0)};
+    const DeviceScene& S = A.scene;
+    const double fd = pose.film_distance;
+    const V3 R = ldv(pose.right), U = ldv(pose.up), F = ldv(pose.forward);
+    // the rule at the rectangle's corners: the block's directions in world space, not normalised
+    V3 pc[4];
+    for (int k = 0; k < 4; ++k) {
+        const camera::Vec d =
+            camera::film_to_world(pose.right, pose.up, pose.forward, fd, (k & 1) ? xhi : xlo, (k & 2) ? yhi : ylo);
+        pc[k] = mk(d.x, d.y, d.z);
+    }
     V3 axis = mk(0.0, 0.0, 0.0);
     for (int i = 0; i < 4; ++i) axis = add(axis, normalize(pc[i]));
     axis = normalize(axis);
     double half = 0.0;
     for (int i = 0; i < 4; ++i) half = fmax(half, vr_angle(axis, pc[i]));
-    const V3 o = mk(A.scene.camera[0], A.scene.camera[1], A.scene.camera[2]);
+    const bool convex = half < 1.5;  // a cone below 90 degrees (1.5708 rad) bounds its corners' hull
+    const V3 o = mk(S.camera[0], S.camera[1], S.camera[2]);
     // a sphere (centre c, radius r) every ray of the block misses
     auto sphere_clear = [&](V3 c, double r) {
         const V3 v = sub(c, o);
         const double dist = sqrt(dot(v, v));
-        if (!(dist > r * (1.0 + 1e-6) + 1e-9)) return false;
+        if (!convex || !(dist > r * (1.0 + 1e-6) + 1e-9)) return false;
         return vr_angle(axis, v) > half + asin(fmin(1.0, r / dist)) + 1e-6;
     };
     bool clear = true;
@@ -1698,13 +1755,14 @@ __global__ __launch_bounds__(256) void block_cull_kernel(RenderArgs A, const Pri
         const Bvh& bv = bvhs[i];
         if (bv.root4 == INT32_MIN) continue;  // an empty mesh never hits
         const double* bb = bv.root_box;
-        // a box wholly in front of the camera: the directions that reach it project (x/z, y/z)
-        // into the bounding rectangle of its corners' projections; clear when that rectangle,
-        // widened by 1e-6 of its scale, misses the block's film rectangle
+        // a box wholly in front of the camera, in camera coordinates: the directions that reach it
+        // project (px/pz, py/pz) into the bounding rectangle of its corners' projections; clear
+        // when that rectangle, widened, misses the block's film rectangle over film_distance
         double ulo = INFINITY, uhi = -INFINITY, vlo = INFINITY, vhi = -INFINITY;
         bool front = true;
         for (int k = 0; k < 8; ++k) {
-            const double px = bb[k & 1] - o.x, py = bb[2 + ((k >> 1) & 1)] - o.y, pz = bb[4 + (k >> 2)] - o.z;
+            const V3 p = mk(bb[k & 1] - o.x, bb[2 + ((k >> 1) & 1)] - o.y, bb[4 + (k >> 2)] - o.z);
+            const double px = dot(p, R), py = dot(p, U), pz = dot(p, F);
             front = front && pz > 1e-6 * (fabs(px) + fabs(py) + fabs(pz));
             ulo = fmin(ulo, px / pz);
             uhi = fmax(uhi, px / pz);
@@ -1712,8 +1770,11 @@ __global__ __launch_bounds__(256) void block_cull_kernel(RenderArgs A, const Pri
             vhi = fmax(vhi, py / pz);
         }
         if (front) {
-            const double mu = 1e-6 * (fabs(ulo) + fabs(uhi) + 1.0), mv = 1e-6 * (fabs(vlo) + fabs(vhi) + 1.0);
-            if (uhi + mu < xlo || ulo - mu > xhi || vhi + mv < ylo || vlo - mv > yhi) continue;
+            // the margin: 1e-6 s^2 covers the transpose standing in for the inverse of a basis that
+            // is orthonormal to 1e-9 (at most 1e-9 s^2 (1 + 1e-9 s), see above) a thousand times over
+            const double s = fmax(fabs(ulo), fabs(uhi)) + fmax(fabs(vlo), fabs(vhi)) + 1.0;
+            const double m = 1e-6 * s * s;
+            if (uhi + m < xlo / fd || ulo - m > xhi / fd || vhi + m < ylo / fd || vlo - m > yhi / fd) continue;
         }
         const V3 c = mk(0.5 * (bb[0] + bb[1]), 0.5 * (bb[2] + bb[3]), 0.5 * (bb[4] + bb[5]));
         const V3 e = mk(bb[1] - bb[0], bb[3] - bb[2], bb[5] - bb[4]);
@@ -1964,16 +2025,23 @@ int launch_accumulate(double* state, const double* photons, uint64_t npix, uint3
 #endif
 }
 
-template <int STACK>
-static hipError_t launch_render_t(const RenderArgs& a, const LaunchChoice& c, int grid_limit, hipStream_t s,
-                                  hipEvent_t mid) {
+// render_kernel<ARGS.., POSED> with ARGS' defaults filled in (POSED is the last template parameter)
+template <bool POSED, int STACK, bool COUNT, bool RECORD, bool DARK0, int MATS = 3, int MINW = 3, bool WHITTED = false,
+          bool COOP = false, bool BIG = false, bool TRACE = false, bool S16 = false>
+struct RenderKernelOf {
+    static constexpr auto fn = &dev::render_kernel<STACK, COUNT, RECORD, DARK0, MATS, MINW, WHITTED, COOP, BIG, TRACE, S16, POSED>;
+};
+
+template <int STACK, bool POSED>
+static hipError_t launch_render_t(const RenderArgs& a, const PoseArgs& pose, const LaunchChoice& c, int grid_limit,
+                                  hipStream_t s, hipEvent_t mid) {
     // persistent waves: enough workgroups to fill the chip, each wave loops over work items
     const uint64_t items = dev::render_items(a, ((a.tile_width + 7) / 8) * ((a.tile_height + 7) / 8) * 64);
     const uint64_t want = (items + 255) / 256;
     dim3 grid((unsigned)(want < (uint64_t)grid_limit ? want : (uint64_t)grid_limit)), block(256);
     const bool recording = c.recording, counting = c.counting;
-#define VR_K(...) hipLaunchKernelGGL((dev::render_kernel<__VA_ARGS__>), grid, block, 0, s, a, a.scene.prims, \
-                                     a.scene.materials, a.scene.bvhs)
+#define VR_K(...) hipLaunchKernelGGL((RenderKernelOf<POSED, __VA_ARGS__>::fn), grid, block, 0, s, a, a.scene.prims, \
+                                     a.scene.materials, a.scene.bvhs, pose)
     if (c.big) {
         // 64-bit load offsets (scenes past 4 GB of triangles or 2^25 wide nodes): the general
         // kernels only (DARK0 = false and every material kind are always correct, only slower), in
@@ -2050,11 +2118,11 @@ static hipError_t launch_render_t(const RenderArgs& a, const LaunchChoice& c, in
     return launch_reduce(a, s, mid);
 }
 
-int launch_block_cull(const RenderArgs& a, uint8_t* mask, void* stream) {
+int launch_block_cull(const RenderArgs& a, const PoseArgs& pose, uint8_t* mask, void* stream) {
     const uint64_t blocks = ((a.tile_width + 7) / 8) * ((a.tile_height + 7) / 8);
     if (blocks == 0) return 0;
     hipLaunchKernelGGL(dev::block_cull_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       a, a.scene.prims, a.scene.bvhs, mask);
+                       a, a.scene.prims, a.scene.bvhs, mask, pose);
     return (int)hipGetLastError();
 }
 
@@ -2072,18 +2140,27 @@ int launch_block_compact(const uint8_t* mask, uint32_t bw, uint32_t bh, bool mor
     return (int)hipGetLastError();
 }
 
-int launch_render(const RenderArgs& a, const LaunchChoice& c, int grid_limit, void* stream, void* mid_event) {
+template <bool POSED>
+static hipError_t launch_render_class(int depth, const RenderArgs& a, const PoseArgs& pose, const LaunchChoice& c,
+                                      int grid_limit, hipStream_t s, hipEvent_t mid) {
+    if (depth <= 24) return launch_render_t<24, POSED>(a, pose, c, grid_limit, s, mid);
+    if (depth <= 32) return launch_render_t<32, POSED>(a, pose, c, grid_limit, s, mid);
+    return launch_render_t<48, POSED>(a, pose, c, grid_limit, s, mid);
+}
+
+int launch_render(const RenderArgs& a, const PoseArgs& pose, const LaunchChoice& c, int grid_limit, void* stream,
+                  void* mid_event) {
     hipStream_t s = (hipStream_t)stream;
     hipEvent_t mid = (hipEvent_t)mid_event;
     if (a.tile_width == 0 || a.tile_height == 0 || a.spp == 0) return 0;
     hipError_t e;
     // the 64-bit-offset kernels exist in the deepest stack class only (a scene that needs them is
     // far larger than any whose tree fits the smaller classes; more LDS is only fewer waves)
-    if (c.big && c.stack_depth <= 48) e = launch_render_t<48>(a, c, grid_limit, s, mid);
-    else if (c.stack_depth <= 24) e = launch_render_t<24>(a, c, grid_limit, s, mid);
-    else if (c.stack_depth <= 32) e = launch_render_t<32>(a, c, grid_limit, s, mid);
-    else if (c.stack_depth <= 48) e = launch_render_t<48>(a, c, grid_limit, s, mid);
-    else return -1000;
+    const int depth = c.big && c.stack_depth <= 48 ? 48 : c.stack_depth;
+    if (depth > 48) return -1000;
+    // RenderArgs::posed: the instantiations whose camera step applies the scene's pose
+    if (a.posed) e = launch_render_class<true>(depth, a, pose, c, grid_limit, s, mid);
+    else e = launch_render_class<false>(depth, a, pose, c, grid_limit, s, mid);
     return (int)e;
 }
 
@@ -2106,7 +2183,7 @@ int launch_trace_probe(const RenderArgs& a, int stack_depth, int minw, bool s16,
     dim3 g((unsigned)grid), b(256);
 #define VR_KT(ST, MW, S16_)                                                                                    \
     hipLaunchKernelGGL((dev::render_kernel<ST, false, false, true, 3, MW, false, false, false, true, S16_>), g, b, \
-                       0, s, a, a.scene.prims, a.scene.materials, a.scene.bvhs)
+                       0, s, a, a.scene.prims, a.scene.materials, a.scene.bvhs, PoseArgs{})
     if (stack_depth > 32) return -1000;
     if (s16) {
         if (minw == 3) VR_KT(32, 3, true);

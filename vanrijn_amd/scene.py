@@ -248,6 +248,44 @@ class SceneSpec:
     integrator: object = None  # None (SimpleRandomIntegrator) or WhittedIntegrator
 
 
+@dataclass(frozen=True)
+class CameraPose:
+    """vr_camera_pose: where the camera is, its orthonormal basis (used as given) and the film's
+    distance along `forward`.  The default is the reference's camera: looking down +z, film at 1.
+    The field of view across the shorter film side is 2 * atan(0.5 / film_distance)."""
+    location: tuple = (0.0, 0.0, 0.0)
+    right: tuple = (1.0, 0.0, 0.0)
+    up: tuple = (0.0, 1.0, 0.0)
+    forward: tuple = (0.0, 0.0, 1.0)
+    film_distance: float = 1.0
+
+    def _c(self):
+        vec = [N.Vec3(*(float(c) for c in v)) for v in (self.location, self.right, self.up, self.forward)]
+        return N.CameraPose(*vec, float(self.film_distance))
+
+    @staticmethod
+    def _from_c(p):
+        return CameraPose(*((v.x, v.y, v.z) for v in (p.location, p.right, p.up, p.forward)), p.film_distance)
+
+    def ray(self, width, height, row, column, ux, uy):
+        """vr_camera_ray: the camera ray of pixel (row, column) with jitter (ux, uy), on the host from
+        the function the kernels compile: (origin, direction), float64 [3] each."""
+        o, d = np.zeros(3), np.zeros(3)
+        p = self._c()
+        N.check(N.lib().vr_camera_ray(C.byref(p), int(width), int(height), int(row), int(column), float(ux),
+                                      float(uy), o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p)))
+        return o, d
+
+
+def look_at(eye, target, up=(0.0, 1.0, 0.0), film_distance=1.0) -> CameraPose:
+    """vr_camera_look_at: the left-handed pose (x right, y up, z forward) of a camera at `eye` looking
+    at `target`; `up` must not be parallel to the view direction."""
+    out = N.CameraPose()
+    e, t, u = (N.Vec3(*(float(c) for c in v)) for v in (eye, target, up))
+    N.check(N.lib().vr_camera_look_at(e, t, u, float(film_distance), C.byref(out)))
+    return CameraPose._from_c(out)
+
+
 class Scene:
     """scene::Scene { camera_location, objects } (src/scene.rs:5-8).
 
@@ -515,6 +553,20 @@ class DeviceScene:
         SceneSpec are not touched."""
         x, y, z = (float(c) for c in xyz)
         N.check(N.lib().vr_scene_set_camera(self.handle, N.Vec3(x, y, z)))
+
+    def set_camera_pose(self, pose: CameraPose):
+        """vr_scene_set_camera_pose: location, orthonormal basis (1e-9; either handedness) and film
+        distance ([1e-3, 1e3]) of the camera every render, film, sample and camera-ray call of this
+        scene uses.  set_camera afterwards moves the location alone.  The owning Scene / SceneSpec are
+        not touched."""
+        p = pose._c()
+        N.check(N.lib().vr_scene_set_camera_pose(self.handle, C.byref(p)))
+
+    def camera_pose(self) -> CameraPose:
+        """The scene's pose (vr_scene_get_camera_pose); the default one until set_camera_pose."""
+        p = N.CameraPose()
+        N.check(N.lib().vr_scene_get_camera_pose(self.handle, C.byref(p)))
+        return CameraPose._from_c(p)
 
     def update_primitives(self, first, prims):
         """vr_scene_update_primitives: replace entries first .. first + len(prims) - 1 of the scene's
