@@ -394,6 +394,56 @@ int vr_camera_look_at(vr_vec3 eye, vr_vec3 target, vr_vec3 up_hint, double film_
 int vr_camera_ray(const vr_camera_pose* pose, uint64_t width, uint64_t height, uint64_t row, uint64_t column,
                   double ux, double uy, double origin[3], double direction[3]);
 
+/* ---------------------------------------------------------------------------------------------
+ * Camera lens: aperture and focus distance (depth of field).  Added under ABI 10
+ * (VR_HAS_CAMERA_LENS).  A thin lens of radius lens_radius lies in the pose's right / up plane at
+ * `location`, focused on the plane focus_distance along `forward`: a point of that plane is sharp, and
+ * the blur of any other grows with lens_radius.  lens_radius == 0 is no lens -- the pinhole of the
+ * section above, bit for bit, with no draw spent -- and every scene has {0, 1} from vr_scene_create on.
+ *
+ * The lens rule.  (x, y) is the sample's film point as above, (lu, lv) in [0, 1) its lens draws.
+ *     (dx, dy) = disc(lu, lv)   Shirley's concentric map (unit_disc.rs:28-40) of ox = 2 lu - 1,
+ *                               oy = 2 lv - 1:  (0, 0) -> (0, 0);
+ *                               |ox| > |oy|:  phi = ((pi / 4) * oy) / ox,  (ox cos phi, ox sin phi);
+ *                               otherwise:    phi = ((pi / 4) * ox) / oy,  (oy sin phi, oy cos phi)
+ *                               with sin and cos the fixed polynomials of vr_camera.h (Taylor through
+ *                               x^15 / x^16, Horner in x^2), within 1.2e-16 of libm's on [-pi/4, pi/4]
+ *     k = film_distance / focus_distance;  a = lens_radius * dx;  b = lens_radius * dy
+ *     origin_c = location_c + (a * right_c + b * up_c)
+ *     d_c = ((x - a * k) * right_c + (y - b * k) * up_c) + film_distance * forward_c
+ * and the ray is origin, d * (1 / |d|): the line from the lens point through the point where the
+ * pinhole ray of (x, y) meets the focus plane.  In f64, in this order, without contraction.
+ * Draws.  In a scene with a lens lu and lv are draws 2 and 3 of the (pixel, sample) stream, Standard
+ * like the jitter, lu first, taken for every sample; the wavelength is draw 4 and the material draws
+ * start at 5, so vr_integrate_params::first_draw = 4 (5 with given wavelengths) replays a lens render.
+ * A scene without a lens keeps its numbering (wavelength 2, materials from 3).
+ * Read by vr_render_tile*, vr_partial_render_scene, vr_film_*, vr_render_samples,
+ * vr_camera_rays_device (whose origins then vary per entry) and the block cull, which stays
+ * conservative under any admitted lens.  No entry point takes a new parameter.
+ * --------------------------------------------------------------------------------------------- */
+#define VR_HAS_CAMERA_LENS 1
+typedef struct vr_camera_lens {
+    double lens_radius, focus_distance;
+} vr_camera_lens;
+/* A scene edit: the contract above applies word for word (blocking; not thread-safe against other calls
+ * on the scene; errors before anything is modified; works on VR_SCENE_HOST_ONLY scenes).  It makes no
+ * device call: the lens is a launch argument.  vr_scene_info::extent and the margins derived from it take
+ * the camera's part as max |location_c| + lens_radius.  vr_scene_set_camera and
+ * vr_scene_set_camera_pose leave the lens alone, and this call leaves the pose alone.
+ * VR_ERROR_INVALID_ARGUMENT: a null argument; an entry that is not finite; lens_radius outside [0, 1e3];
+ * focus_distance outside [1e-3, 1e6]. */
+int vr_scene_set_camera_lens(vr_scene* scene, const vr_camera_lens* lens);
+int vr_scene_get_camera_lens(const vr_scene* scene, vr_camera_lens* out);
+/* disc(lu, lv) on the host, unit radius, from the inline function the kernels compile.
+ * VR_ERROR_INVALID_ARGUMENT: a null out. */
+int vr_camera_lens_point(double lu, double lv, double out[2]);
+/* The lens rule on the host, from the same inline functions: the ray of pixel (row, column) with jitter
+ * (ux, uy) and lens draws (lu, lv).  Pose and lens are used as given (not validated); lens_radius == 0
+ * returns vr_camera_ray's bits.  VR_ERROR_INVALID_ARGUMENT: as vr_camera_ray. */
+int vr_camera_lens_ray(const vr_camera_pose* pose, const vr_camera_lens* lens, uint64_t width, uint64_t height,
+                       uint64_t row, uint64_t column, double ux, double uy, double lu, double lv, double origin[3],
+                       double direction[3]);
+
 /* util::Tile (src/util/tile_iterator.rs:1-7): half-open row/column ranges of the full image. */
 typedef struct vr_tile {
     uint64_t start_column, end_column, start_row, end_row;

@@ -9,8 +9,12 @@ one device, one stream), after warm-up rounds:
            through the mesh, turned to keep the mesh in view;
   staged   the posed view as a caller had to build it before poses: vr_camera_rays_device +
            vr_integrate_rays_device + vr_accumulate_photons_device, HIP events around the three.
-Median and best per leg, staged / posed, the counters of one untimed counting launch per view (hit rate and
-culled share move with the view), and a check that the staged records equal the posed render's bit for bit.
+  lens     the default pose with a thin lens (radius 0.05, focused on the mesh's centre): the render kernel's
+           lens instantiations; the default leg is the pinhole of the same view;
+  lens_staged  that view through the staged pipeline (first_draw = 4: the lens spends draws 2 and 3).
+Median and best per leg, staged / posed, lens_staged / lens, lens / default, the counters of one untimed counting launch per view (hit rate and
+culled share move with the view), and checks that the staged records equal the posed render's and the lens
+render's bit for bit.
 Prints one JSON line (and writes it to --out).
 """
 import argparse
@@ -27,11 +31,12 @@ import torch  # noqa: E402
 from vanrijn_amd import scenes  # noqa: E402
 from vanrijn_amd.render import (Tile, accumulate_photons_device, camera_rays_device, integrate_rays_device,  # noqa: E402
                                 render_tile_device, stream_check_error)
-from vanrijn_amd.scene import CameraPose, DeviceScene, look_at  # noqa: E402
+from vanrijn_amd.scene import CameraLens, CameraPose, DeviceScene, look_at  # noqa: E402
 
 SEED = 0x5EED0001
 MESH_CENTRE = (-1.7, -0.8, 0.0)  # scenes.procedural_bunny
 ORBIT_DEGREES = 40.0
+LENS_RADIUS = 0.05
 
 
 def orbit_pose(camera, degrees):
@@ -52,9 +57,11 @@ def counters_of(ds, tile, size, spp, state, sp):
 
 def run(size, spp, rounds, warmup):
     spec = scenes.main_scene().spec()
-    default, posed = DeviceScene(spec, 0), DeviceScene(spec, 0)
+    default, posed, lensed = DeviceScene(spec, 0), DeviceScene(spec, 0), DeviceScene(spec, 0)
     pose = orbit_pose(spec.camera_location, ORBIT_DEGREES)
     posed.set_camera_pose(pose)
+    lens = CameraLens(LENS_RADIUS, math.dist(spec.camera_location, MESH_CENTRE))
+    lensed.set_camera_lens(lens)
     tile = Tile(0, size, 0, size)
     npix, n = size * size, size * size * spp
     stream = torch.cuda.Stream()
@@ -66,19 +73,29 @@ def run(size, spp, rounds, warmup):
         ph = torch.zeros(n * 2, dtype=torch.float64, device="cuda")
         staged = torch.zeros(npix * 8, dtype=torch.float64, device="cuda")
         direct = torch.zeros(npix * 8, dtype=torch.float64, device="cuda")
+        lens_staged = torch.zeros(npix * 8, dtype=torch.float64, device="cuda")
+        lens_direct = torch.zeros(npix * 8, dtype=torch.float64, device="cuda")
         other = torch.zeros(npix * 8, dtype=torch.float64, device="cuda")
     stream.synchronize()
-    times = {"default": [], "default_reduce": [], "posed": [], "posed_reduce": [], "staged": []}
+    times = {"default": [], "default_reduce": [], "posed": [], "posed_reduce": [], "staged": [], "lens": [],
+             "lens_reduce": [], "lens_staged": []}
+
+    def staged_pipeline(ds, first_draw, into):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        camera_rays_device(ds, tile, size, size, spp, SEED, 0, o.data_ptr(), d.data_ptr(), ids.data_ptr(), sp)
+        integrate_rays_device(ds, n, o.data_ptr(), d.data_ptr(), ph.data_ptr(), SEED, stream_ids_ptr=ids.data_ptr(),
+                              first_draw=first_draw, stream_ptr=sp)
+        accumulate_photons_device(into.data_ptr(), ph.data_ptr(), npix, spp, stream_ptr=sp)
+        e1.record(stream)
+        return e0, e1
+
     for r in range(warmup + rounds):
         sd = render_tile_device(default, tile, size, size, spp, SEED, 0, other.data_ptr(), sp, timed=True)
         spo = render_tile_device(posed, tile, size, size, spp, SEED, 0, direct.data_ptr(), sp, timed=True)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        camera_rays_device(posed, tile, size, size, spp, SEED, 0, o.data_ptr(), d.data_ptr(), ids.data_ptr(), sp)
-        integrate_rays_device(posed, n, o.data_ptr(), d.data_ptr(), ph.data_ptr(), SEED, stream_ids_ptr=ids.data_ptr(),
-                              first_draw=2, stream_ptr=sp)
-        accumulate_photons_device(staged.data_ptr(), ph.data_ptr(), npix, spp, stream_ptr=sp)
-        e1.record(stream)
+        e0, e1 = staged_pipeline(posed, 2, staged)
+        sl = render_tile_device(lensed, tile, size, size, spp, SEED, 0, lens_direct.data_ptr(), sp, timed=True)
+        l0, l1 = staged_pipeline(lensed, 4, lens_staged)
         stream.synchronize()
         if r >= warmup:
             times["default"].append(sd["kernel_ms"])
@@ -86,19 +103,29 @@ def run(size, spp, rounds, warmup):
             times["posed"].append(spo["kernel_ms"])
             times["posed_reduce"].append(spo["reduce_ms"])
             times["staged"].append(e0.elapsed_time(e1))
+            times["lens"].append(sl["kernel_ms"])
+            times["lens_reduce"].append(sl["reduce_ms"])
+            times["lens_staged"].append(l0.elapsed_time(l1))
     stream_check_error(posed, sp)
+    stream_check_error(lensed, sp)
     equal = bool(torch.equal(staged.view(torch.int64), direct.view(torch.int64)))
+    lens_equal = bool(torch.equal(lens_staged.view(torch.int64), lens_direct.view(torch.int64)))
     out = {"size": size, "spp": spp, "samples": n, "orbit_degrees": ORBIT_DEGREES,
            "pose": {k: getattr(pose, k) for k in CameraPose.__dataclass_fields__},
-           "staged_equals_posed_render": equal, "legs": {},
+           "staged_equals_posed_render": equal,
+           "lens": {"lens_radius": lens.lens_radius, "focus_distance": lens.focus_distance},
+           "staged_equals_lens_render": lens_equal, "legs": {},
            "counters": {"default": counters_of(default, tile, size, spp, other, sp),
-                        "posed": counters_of(posed, tile, size, spp, other, sp)}}
+                        "posed": counters_of(posed, tile, size, spp, other, sp),
+                        "lens": counters_of(lensed, tile, size, spp, other, sp)}}
     stream.synchronize()
     for leg, t in times.items():
         out["legs"][leg] = {"ms_median": round(statistics.median(t), 4), "ms_min": round(min(t), 4)}
     med = {leg: statistics.median(t) for leg, t in times.items()}
     out["staged_over_posed"] = round(med["staged"] / (med["posed"] + med["posed_reduce"]), 3)
     out["posed_over_default"] = round(med["posed"] / med["default"], 3)
+    out["lens_staged_over_lens"] = round(med["lens_staged"] / (med["lens"] + med["lens_reduce"]), 3)
+    out["lens_over_default"] = round(med["lens"] / med["default"], 3)
     return out
 
 
@@ -122,6 +149,8 @@ def main():
             f.write(line + "\n")
     if not result["staged_equals_posed_render"]:
         sys.exit("the staged pipeline's records differ from the posed render's")
+    if not result["staged_equals_lens_render"]:
+        sys.exit("the staged pipeline's records differ from the lens render's")
 
 
 if __name__ == "__main__":

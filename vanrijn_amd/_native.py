@@ -45,6 +45,10 @@ class CameraPose(C.Structure):
     _fields_ = [("location", Vec3), ("right", Vec3), ("up", Vec3), ("forward", Vec3), ("film_distance", C.c_double)]
 
 
+class CameraLens(C.Structure):
+    _fields_ = [("lens_radius", C.c_double), ("focus_distance", C.c_double)]
+
+
 class Spectrum(C.Structure):
     _fields_ = [("shortest_wavelength", C.c_double), ("longest_wavelength", C.c_double),
                 ("sample_count", C.c_uint32), ("samples", C.POINTER(C.c_double))]
@@ -190,6 +194,11 @@ SIGNATURES = {
     "vr_scene_get_camera_pose": (C.c_int, [_p, C.POINTER(CameraPose)]),
     "vr_camera_look_at": (C.c_int, [Vec3, Vec3, Vec3, _d, C.POINTER(CameraPose)]),
     "vr_camera_ray": (C.c_int, [C.POINTER(CameraPose), _u64, _u64, _u64, _u64, _d, _d, _p, _p]),
+    "vr_scene_set_camera_lens": (C.c_int, [_p, C.POINTER(CameraLens)]),
+    "vr_scene_get_camera_lens": (C.c_int, [_p, C.POINTER(CameraLens)]),
+    "vr_camera_lens_point": (C.c_int, [_d, _d, _p]),
+    "vr_camera_lens_ray": (C.c_int, [C.POINTER(CameraPose), C.POINTER(CameraLens), _u64, _u64, _u64, _u64, _d, _d, _d, _d,
+                                     _p, _p]),
     "vr_partial_render_scene": (C.c_int, [_p, TileC, _u64, _u64, C.POINTER(AccumulationBufferC)]),
     "vr_render_tile": (C.c_int, [_p, C.POINTER(RenderParams), C.POINTER(AccumulationBufferC)]),
     "vr_render_tile_device": (C.c_int, [_p, C.POINTER(RenderParams), _p, _p, _u32, C.POINTER(LaunchStats)]),

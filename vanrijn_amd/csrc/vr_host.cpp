@@ -257,6 +257,7 @@ vr::RenderArgs make_args(const vr_scene* s, const vr_render_params* p, double* s
                                  d.up[2], d.forward[0], d.forward[1], d.forward[2], d.film_distance};
         const double standard[10] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 1.0};
         a.posed = std::equal(pose, pose + 10, standard) ? 0u : 1u;
+        if (s->lens.lens_radius != 0.0) a.posed = 2u;  // a lens: the instantiations that apply pose and lens
     }
     {
         const uint64_t bw = (a.tile_width + 7) / 8, bh = (a.tile_height + 7) / 8;
@@ -411,7 +412,7 @@ int enqueue_passes(vr_scene* s, CallCtx* c, const vr_render_params* p, double* s
         if (rc) return rc;
         if (nb >= (1ull << 32)) return fail(VR_ERROR_UNSUPPORTED, "too many pixel blocks in one tile (2^32)");
         vr::RenderArgs a = make_args(s, p, state);
-        int lc = vr::launch_block_cull(a, s->pose, (uint8_t*)c->mask, st);
+        int lc = vr::launch_block_cull(a, s->pose, s->lens, (uint8_t*)c->mask, st);
         uint32_t* lst = (uint32_t*)((char*)c->mask + list_off);
         const char* bm = tuning_env("VR_BLOCK_MORTON");  // tuning hook: live blocks in Z-order
         const bool morton = bm ? atoi(bm) != 0 : (s->mats & 2) == 0;  // with block-major items (make_args)
@@ -494,7 +495,7 @@ int enqueue_passes(vr_scene* s, CallCtx* c, const vr_render_params* p, double* s
                        (lc.s16 ? VR_VARIANT_STACK16 : 0u);
         // the COOP instantiations (2 waves per SIMD) keep 3 workgroups per CU (coop_grid_per_cu)
         const int per_cu = lc.coop ? coop_grid_per_cu() : grid_per_cu();
-        int lr = vr::launch_render(a, s->pose, lc, std::max(1, s->cu_count) * per_cu, st, mid);
+        int lr = vr::launch_render(a, s->pose, s->lens, lc, std::max(1, s->cu_count) * per_cu, st, mid);
         if (lr) return launch_status(lr);
         if (timing) {
             hipEvent_t end = timing->add();

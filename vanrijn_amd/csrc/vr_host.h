@@ -89,6 +89,8 @@ struct vr_scene {
     double camera[3];
     // the camera pose beside the location (vr_scene_set_camera_pose): the default is the reference's camera
     vr::PoseArgs pose = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}, 1.0};
+    // the camera lens (vr_scene_set_camera_lens): radius 0 is no lens
+    vr::LensArgs lens = {0.0, 1.0};
     double extent = 0.0;
     std::vector<vr::Material> materials;
     std::vector<vr::Prim> prims;

@@ -371,6 +371,21 @@ int vr_scene_set_camera_pose(vr_scene* s, const vr_camera_pose* pose) {
     return vr_scene_set_camera(s, pose->location);  // cannot fail: the location is finite
 }
 
+int vr_scene_set_camera_lens(vr_scene* s, const vr_camera_lens* lens) {
+    if (!s || !lens) return fail(VR_ERROR_INVALID_ARGUMENT, "null scene or lens");
+    if (!std::isfinite(lens->lens_radius) || !std::isfinite(lens->focus_distance))
+        return fail(VR_ERROR_INVALID_ARGUMENT, "camera lens: an entry is not finite");
+    if (!(lens->lens_radius >= 0.0 && lens->lens_radius <= 1e3))
+        return fail(VR_ERROR_INVALID_ARGUMENT, "camera lens: lens_radius outside [0, 1e3]");
+    if (!(lens->focus_distance >= 1e-3 && lens->focus_distance <= 1e6))
+        return fail(VR_ERROR_INVALID_ARGUMENT, "camera lens: focus_distance outside [1e-3, 1e6]");
+    s->lens.lens_radius = lens->lens_radius;
+    s->lens.focus_distance = lens->focus_distance;
+    update_base_extent(s);  // the camera's part of the extent carries the radius
+    update_scalars(s);
+    return VR_OK;
+}
+
 int vr_camera_look_at(vr_vec3 eye, vr_vec3 target, vr_vec3 up_hint, double film_distance, vr_camera_pose* out) {
     if (!out) return fail(VR_ERROR_INVALID_ARGUMENT, "null pose");
     if (!finite3(eye) || !finite3(target) || !finite3(up_hint) || !std::isfinite(film_distance))

@@ -258,6 +258,7 @@ int vr_camera_rays_device(const vr_scene* s, const vr_render_params* p, double* 
     vr::CameraRaysArgs a{};
     for (int k = 0; k < 3; ++k) a.camera[k] = s->dev.camera[k];
     a.pose = s->pose;
+    a.lens = s->lens;
     a.start_column = r.start_column;
     a.start_row = r.start_row;
     a.tile_width = r.tile_width;
@@ -276,3 +277,32 @@ int vr_camera_rays_device(const vr_scene* s, const vr_render_params* p, double* 
     return VR_OK;
 }
 
+int vr_camera_lens_point(double lu, double lv, double out[2]) {
+    if (!out) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
+    vr::camera::lens_disc(lu, lv, &out[0], &out[1]);
+    return VR_OK;
+}
+
+int vr_camera_lens_ray(const vr_camera_pose* pose, const vr_camera_lens* lens, uint64_t width, uint64_t height, uint64_t row,
+                       uint64_t column, double ux, double uy, double lu, double lv, double origin[3], double direction[3]) {
+    if (!pose || !lens || !origin || !direction) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
+    // no lens: the pinhole ray, whose origin is the location's bits
+    if (lens->lens_radius == 0.0) return vr_camera_ray(pose, width, height, row, column, ux, uy, origin, direction);
+    if (width == 0 || height == 0 || row >= height || column >= width)
+        return fail(VR_ERROR_INVALID_ARGUMENT, "camera ray: the pixel is outside the image");
+    double film[4];
+    vr::camera::film_constants(width, height, film);
+    const double l[3] = {pose->location.x, pose->location.y, pose->location.z};
+    const double r[3] = {pose->right.x, pose->right.y, pose->right.z}, u[3] = {pose->up.x, pose->up.y, pose->up.z};
+    const double f[3] = {pose->forward.x, pose->forward.y, pose->forward.z};
+    vr::camera::Vec o, d;
+    vr::camera::lens_ray(l, r, u, f, pose->film_distance, lens->lens_radius, lens->focus_distance,
+                         vr::camera::film_x(film, column, ux), vr::camera::film_y(film, height, row, uy), lu, lv, &o, &d);
+    origin[0] = o.x;
+    origin[1] = o.y;
+    origin[2] = o.z;
+    direction[0] = d.x;
+    direction[1] = d.y;
+    direction[2] = d.z;
+    return VR_OK;
+}

@@ -149,7 +149,9 @@ const char* prim_row(const vr_primitive_desc& p, int32_t object, int32_t positio
 // base_extent: the camera's and every primitive row's share of the extent (a row keeps the entry's
 // scalar, and a sphere's centre, as given)
 void update_base_extent(vr_scene* s) {
-    double extent = std::max({std::fabs(s->camera[0]), std::fabs(s->camera[1]), std::fabs(s->camera[2])});
+    // the camera's part: every point of the lens disc is within lens_radius of the location
+    double extent =
+        std::max({std::fabs(s->camera[0]), std::fabs(s->camera[1]), std::fabs(s->camera[2])}) + s->lens.lens_radius;
     for (const vr::Prim& p : s->prims) {
         if (p.kind == VR_PRIMITIVE_PLANE)
             extent = std::max(extent, std::fabs(p.scalar));
@@ -613,6 +615,13 @@ int vr_scene_get_camera_pose(const vr_scene* s, vr_camera_pose* out) {
     out->up = vr_vec3{d.up[0], d.up[1], d.up[2]};
     out->forward = vr_vec3{d.forward[0], d.forward[1], d.forward[2]};
     out->film_distance = d.film_distance;
+    return VR_OK;
+}
+
+int vr_scene_get_camera_lens(const vr_scene* s, vr_camera_lens* out) {
+    if (!s || !out) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
+    out->lens_radius = s->lens.lens_radius;
+    out->focus_distance = s->lens.focus_distance;
     return VR_OK;
 }
 

@@ -269,7 +269,7 @@ __global__ __launch_bounds__(256) void integrate_kernel(IntegrateArgs A) {
 
 // ImageSampler::ray_for_pixel (camera.rs:24-66) for entry j = s * (tile pixels) + p: render_kernel's
 // camera step (the jitter is draws 0 and 1 of the (pixel, sample) stream, x before y) under the
-// scene's pose: vr_camera.h's rule
+// scene's pose: vr_camera.h's rule; under a lens the lens rule, with draws 2 and 3, and an origin per entry
 __global__ __launch_bounds__(256) void camera_rays_kernel(CameraRaysArgs A) {
     const uint64_t npix = A.tile_width * A.tile_height;
     const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -284,10 +284,21 @@ __global__ __launch_bounds__(256) void camera_rays_kernel(CameraRaysArgs A) {
     const double uy = rng.standard();
     const double x = camera::film_x(A.film, col, ux);
     const double y = camera::film_y(A.film, A.height, row, uy);
-    const camera::Vec d = camera::ray_direction(A.pose.right, A.pose.up, A.pose.forward, A.pose.film_distance, x, y);
-    A.origins[3 * j] = A.camera[0];
-    A.origins[3 * j + 1] = A.camera[1];
-    A.origins[3 * j + 2] = A.camera[2];
+    camera::Vec o, d;
+    if (A.lens.lens_radius != 0.0) {  // a lens: draws 2 and 3, then the lens rule (vr_camera.h)
+        const double lu = rng.standard();
+        const double lv = rng.standard();
+        camera::lens_ray(A.camera, A.pose.right, A.pose.up, A.pose.forward, A.pose.film_distance, A.lens.lens_radius,
+                         A.lens.focus_distance, x, y, lu, lv, &o, &d);
+    } else {
+        o.x = A.camera[0];
+        o.y = A.camera[1];
+        o.z = A.camera[2];
+        d = camera::ray_direction(A.pose.right, A.pose.up, A.pose.forward, A.pose.film_distance, x, y);
+    }
+    A.origins[3 * j] = o.x;
+    A.origins[3 * j + 1] = o.y;
+    A.origins[3 * j + 2] = o.z;
     A.directions[3 * j] = d.x;
     A.directions[3 * j + 1] = d.y;
     A.directions[3 * j + 2] = d.z;

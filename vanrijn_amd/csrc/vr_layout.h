@@ -151,6 +151,14 @@ struct PoseArgs {
     double film_distance;
 };
 
+// The camera lens (vr_camera.h: the lens rule): a thin lens of radius lens_radius in the right / up
+// plane at the location, focused on the plane focus_distance along `forward`; lens_radius 0 is no
+// lens, the default.  The render kernel and the block cull take it after PoseArgs, last, for PoseArgs'
+// reason (DESIGN.md section 2 "Camera lens").
+struct LensArgs {
+    double lens_radius, focus_distance;
+};
+
 struct RenderArgs {
     DeviceScene scene;
     uint64_t start_column, start_row, tile_width, tile_height;
@@ -222,7 +230,8 @@ struct RenderArgs {
     uint32_t* stage_tag;  // [pass sample][tile pixel], or nullptr
     uint32_t stage_gen;   // this pass's generation (never 0)
     // 1: the scene's pose is not the default one and the camera step loads it (vr_render.hip
-    // load_pose_args); 0: the step forms normalize((x, y, 1)), which the rule gives for the default pose
+    // load_pose_args); 0: the step forms normalize((x, y, 1)), which the rule gives for the default pose;
+    // 2: the scene has a lens (lens_radius != 0) and the step applies pose and lens, whatever the pose
     uint32_t posed;
 };
 
@@ -269,6 +278,7 @@ struct IntegrateArgs {
 struct CameraRaysArgs {
     double camera[3];
     PoseArgs pose;
+    LensArgs lens;               // lens_radius != 0: the lens rule and draws 2 and 3 (lu, lv)
     uint64_t start_column, start_row, tile_width, tile_height;
     uint64_t width, height;
     uint64_t seed_key, first_sample;
@@ -315,11 +325,11 @@ struct LaunchChoice {
     bool big;         // 64-bit node / triangle load offsets (vr_host.cpp needs_big_offsets)
     bool s16;         // 16-bit LDS stack entries (trees below 65,536 wide nodes; timed kernels only)
 };
-int launch_render(const RenderArgs& args, const PoseArgs& pose, const LaunchChoice& choice, int grid_limit, void* stream,
-                  void* mid_event = nullptr);
+int launch_render(const RenderArgs& args, const PoseArgs& pose, const LensArgs& lens, const LaunchChoice& choice,
+                  int grid_limit, void* stream, void* mid_event = nullptr);
 // vr_image.hip: records (from_state = 1, RenderArgs::state's layout) or XYZ colour (3 f64) -> sRGB8
 // the camera-frustum test of every 8x8 block of a launch's tile into mask (RenderArgs::block_mask)
-int launch_block_cull(const RenderArgs& args, const PoseArgs& pose, uint8_t* mask, void* stream);
+int launch_block_cull(const RenderArgs& args, const PoseArgs& pose, const LensArgs& lens, uint8_t* mask, void* stream);
 // the live (unculled) blocks of `mask` (n blocks) in order into live[], their number into *count
 int launch_block_compact(const uint8_t* mask, uint32_t bw, uint32_t bh, bool morton, uint32_t* live, uint32_t* count,
                          void* stream);

@@ -189,6 +189,7 @@ struct RenderKernargs {  // render_kernel's argument list as the segment holds i
     const Material* materials;
     const Bvh* bvhs;
     PoseArgs pose;
+    LensArgs lens;
 };
 __device__ __forceinline__ camera::Vec posed_direction(double x, double y) {
     typedef __attribute__((address_space(4))) const RenderKernargs* Segment;
@@ -198,6 +199,19 @@ __device__ __forceinline__ camera::Vec posed_direction(double x, double y) {
     const double u[3] = {k->pose.up[0], k->pose.up[1], k->pose.up[2]};
     const double f[3] = {k->pose.forward[0], k->pose.forward[1], k->pose.forward[2]};
     return camera::ray_direction(r, u, f, k->pose.film_distance, x, y);
+}
+// The lens rule (vr_camera.h) from pose and lens, the kernel's last two arguments, read the same way:
+// twelve scalar loads per camera ray of a wave, in the lens instantiations only
+__device__ __forceinline__ void lens_camera_ray(const double location[3], double x, double y, double lu, double lv,
+                                                camera::Vec* o, camera::Vec* d) {
+    typedef __attribute__((address_space(4))) const RenderKernargs* Segment;
+    Segment k = (Segment)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    const double r[3] = {k->pose.right[0], k->pose.right[1], k->pose.right[2]};
+    const double u[3] = {k->pose.up[0], k->pose.up[1], k->pose.up[2]};
+    const double f[3] = {k->pose.forward[0], k->pose.forward[1], k->pose.forward[2]};
+    camera::lens_ray(location, r, u, f, k->pose.film_distance, k->lens.lens_radius, k->lens.focus_distance, x, y, lu, lv,
+                     o, d);
 }
 
 // MATS: material kinds present (1 Lambertian, 2 reflective, 3 both); code for absent kinds is
@@ -214,18 +228,20 @@ __device__ __forceinline__ camera::Vec posed_direction(double x, double y) {
 // object) instead of shading, and no path state exists, so the register peak is traversal's alone.
 // S16: 16-bit LDS stack entries (trees below 65,536 wide nodes): half the stack's LDS, so more
 // workgroups fit a CU.
-// POSED: the camera step applies the scene's pose (RenderArgs::posed).  The default pose keeps its own
-// instantiations, whose code is what it was before poses existed: in a kernel whose registers are all
-// taken, a pose read in the shared code moved spills and scratch of a dozen instantiations whichever way
-// it was loaded (DESIGN.md section 2 "Camera pose").
+// CAM: the camera step's mode (RenderArgs::posed): 0 the default pose, 1 the scene's pose, 2 the scene's
+// pose and lens (any pose, the default one included; two more draws per sample).  The default pose keeps
+// its own instantiations, whose code is what it was before poses existed: in a kernel whose registers are
+// all taken, a pose read in the shared code moved spills and scratch of a dozen instantiations whichever
+// way it was loaded (DESIGN.md section 2 "Camera pose"); the lens keeps its own for the same reason, so
+// the posed ones are what they were before lenses existed ("Camera lens").
 template <int STACK, bool COUNT, bool RECORD, bool DARK0, int MATS = 3, int MINW = 3, bool WHITTED = false,
-          bool COOP = false, bool BIG = false, bool TRACE = false, bool S16 = false, bool POSED = false>
+          bool COOP = false, bool BIG = false, bool TRACE = false, bool S16 = false, int CAM = 0>
 // The scene's small uniform tables (planes / spheres, materials, BVH roots) come in again as
 // restrict-qualified arguments: nothing the kernel stores can alias them, so their wave-uniform
 // reads compile to scalar loads (the scalar cache) instead of vector loads through L2.
 __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const Prim* __restrict__ g_prims,
                                                            const Material* __restrict__ g_materials,
-                                                           const Bvh* __restrict__ g_bvhs, PoseArgs) {
+                                                           const Bvh* __restrict__ g_bvhs, PoseArgs, LensArgs) {
     typedef typename std::conditional<S16, uint16_t, uint32_t>::type StackT;
     __shared__ StackT st_node[STACK * 256];
     // leaf triangles met during traversal wait for a leaf round, in which every lane tests one: the
@@ -1387,7 +1403,14 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                 bounces = 0;
                 flags = 0;
                 pre.o = mk(S.camera[0], S.camera[1], S.camera[2]);
-                if constexpr (POSED) {  // the scene's pose (vr_camera.h: the ray rule)
+                if constexpr (CAM == 2) {  // pose and lens (vr_camera.h: the lens rule); draws 2 and 3
+                    const double lu = rng.standard();
+                    const double lv = rng.standard();
+                    camera::Vec co, cd;
+                    lens_camera_ray(S.camera, x, y, lu, lv, &co, &cd);
+                    pre.o = mk(co.x, co.y, co.z);
+                    pre.d = mk(cd.x, cd.y, cd.z);
+                } else if constexpr (CAM == 1) {  // the scene's pose (vr_camera.h: the ray rule)
                     const camera::Vec cd = posed_direction(x, y);
                     pre.d = mk(cd.x, cd.y, cd.z);
                 } else {  // the default pose: what the rule gives for it, bit for bit (vr_camera.h)
@@ -1684,13 +1707,32 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
 //    half-angle (attained at a corner) plus the sphere's angular radius plus 1e-6 rad.  A cone of
 //    half-angle below 90 degrees is convex, so holding the four corner directions it holds every
 //    positive combination of them: every direction of the block (a wider cone is not used).
+// Under a lens (vr_camera.h: the lens rule) a sample's ray leaves the lens point o' = o + a right + b up,
+// |(a, b)| <= lens_radius * |disc| with |disc| <= 1 + a few ulp, and its direction is the pinhole
+// direction of the film point (x - a k, y - b k), k = film_distance / focus_distance.  With rho =
+// lens_radius (1 + 1e-6) -- the disc's excess, the products' rounding and the 1e-9 the basis may be off
+// orthonormal (|a right + b up| <= |(a, b)| sqrt(1 + 2e-9)) a hundred times over -- two widenings
+// carry every test over, and with lens_radius 0 every number below is what it was:
+//  * directions: the block's film rectangle grows by rho k on each side before the corner directions
+//    are formed, so the parallelogram and the cone hold every lens ray's direction;
+//  * origins: a ray from o' that meets a sphere (c, r) runs within |o' - o| <= rho of the same
+//    direction's ray from o, which then meets the sphere (c, r + rho): spheres, and boxes' bounding
+//    spheres, are tested from o with their radius inflated by rho.  A plane's num from o' is off its
+//    value from o by (o' - o) . n, at most rho |n|: |num| must exceed its tolerance plus rho |n|, and
+//    then keeps its sign over the lens.  A box corner seen from o' has camera coordinates (px - a', py
+//    - b', pz - c') with |a'|, |b'| <= rho and |c'| <= 1e-6 lens_radius (a right . forward + b up .
+//    forward, at most 2e-9 of it): the front test must hold for the smallest pz and the largest |px|,
+//    |py|, and the bounding rectangle takes each corner's extremes (px +- rho) / pz over both ends of
+//    pz's range (a quotient monotone in pz takes its extremes there).
+// A lens so wide that nothing can be proved -- a cone past 90 degrees, corner directions on both sides
+// of every plane -- leaves every block live: slower, never wrong.
 // Each sample of a culled block is then exactly the missed camera ray's photon {0, 0}, whatever
 // its random draws.
 __device__ __forceinline__ double vr_angle(V3 a, V3 b) {
     return atan2(sqrt(dot(cross(a, b), cross(a, b))), dot(a, b));
 }
 __global__ __launch_bounds__(256) void block_cull_kernel(RenderArgs A, const Prim* prims, const Bvh* bvhs,
-                                                         uint8_t* mask, PoseArgs pose) {
+                                                         uint8_t* mask, PoseArgs pose, LensArgs lens) {
     const uint32_t bw = (uint32_t)((A.tile_width + 7) / 8), bh = (uint32_t)((A.tile_height + 7) / 8);
     const uint32_t b = blockIdx.x * 256 + threadIdx.x;
     if (b >= bw * bh) return;
@@ -1703,10 +1745,13 @@ __global__ __launch_bounds__(256) void block_cull_kernel(RenderArgs A, const Pri
     const double xa = c0 * A.film[0] - A.film[1], xb = c1 * A.film[0] - A.film[1];
     const double ya = (H - r1) * A.film[2] - A.film[3], yb = (H - r0) * A.film[2] - A.film[3];
     const double mx = 1e-9 * (fabs(xa) + fabs(xb) + 1.0), my = 1e-9 * (fabs(ya) + fabs(yb) + 1.0);
-    const double xlo = fmin(xa, xb) - mx, xhi = fmax(xa, xb) + mx;
-    const double ylo = fmin(ya, yb) - my, yhi = fmax(ya, yb) + my;
     const DeviceScene& S = A.scene;
     const double fd = pose.film_distance;
+    // the lens: rho bounds the lens point's distance from the location, rho k the film point's shift
+    const double rho = lens.lens_radius * (1.0 + 1e-6), dz = 1e-6 * lens.lens_radius;
+    const double lw = rho * (fd / lens.focus_distance);
+    const double xlo = (fmin(xa, xb) - mx) - lw, xhi = (fmax(xa, xb) + mx) + lw;
+    const double ylo = (fmin(ya, yb) - my) - lw, yhi = (fmax(ya, yb) + my) + lw;
     const V3 R = ldv(pose.right), U = ldv(pose.up), F = ldv(pose.forward);
     // the rule at the rectangle's corners: the block's directions in world space, not normalised
     V3 pc[4];
@@ -1723,7 +1768,8 @@ __global__ __launch_bounds__(256) void block_cull_kernel(RenderArgs A, const Pri
     const bool convex = half < 1.5;  // a cone below 90 degrees (1.5708 rad) bounds its corners' hull
     const V3 o = mk(S.camera[0], S.camera[1], S.camera[2]);
     // a sphere (centre c, radius r) every ray of the block misses
-    auto sphere_clear = [&](V3 c, double r) {
+    auto sphere_clear = [&](V3 c, double r0) {
+        const double r = r0 + rho;  // the lens' origins (above)
         const V3 v = sub(c, o);
         const double dist = sqrt(dot(v, v));
         if (!convex || !(dist > r * (1.0 + 1e-6) + 1e-9)) return false;
@@ -1738,7 +1784,7 @@ __global__ __launch_bounds__(256) void block_cull_kernel(RenderArgs A, const Pri
             const double num = dot(sub(q, o), c);
             const double nn = sqrt(dot(c, c));
             const double tol = 1e-9 * nn * (sqrt(dot(q, q)) + sqrt(dot(o, o)) + 1.0);
-            if (!(fabs(num) > tol)) {
+            if (!(fabs(num) > tol + rho * nn)) {
                 clear = false;
                 break;
             }
@@ -1763,11 +1809,12 @@ __global__ __launch_bounds__(256) void block_cull_kernel(RenderArgs A, const Pri
         for (int k = 0; k < 8; ++k) {
             const V3 p = mk(bb[k & 1] - o.x, bb[2 + ((k >> 1) & 1)] - o.y, bb[4 + (k >> 2)] - o.z);
             const double px = dot(p, R), py = dot(p, U), pz = dot(p, F);
-            front = front && pz > 1e-6 * (fabs(px) + fabs(py) + fabs(pz));
-            ulo = fmin(ulo, px / pz);
-            uhi = fmax(uhi, px / pz);
-            vlo = fmin(vlo, py / pz);
-            vhi = fmax(vhi, py / pz);
+            const double pzl = pz - dz, pzh = pz + dz;  // pz over the lens' origins; pz itself without a lens
+            front = front && pzl > 1e-6 * ((fabs(px) + rho) + (fabs(py) + rho) + fabs(pz));
+            ulo = fmin(ulo, fmin((px - rho) / pzl, (px - rho) / pzh));
+            uhi = fmax(uhi, fmax((px + rho) / pzl, (px + rho) / pzh));
+            vlo = fmin(vlo, fmin((py - rho) / pzl, (py - rho) / pzh));
+            vhi = fmax(vhi, fmax((py + rho) / pzl, (py + rho) / pzh));
         }
         if (front) {
             // the margin: 1e-6 s^2 covers the transpose standing in for the inverse of a basis that
@@ -2025,23 +2072,23 @@ int launch_accumulate(double* state, const double* photons, uint64_t npix, uint3
 #endif
 }
 
-// render_kernel<ARGS.., POSED> with ARGS' defaults filled in (POSED is the last template parameter)
-template <bool POSED, int STACK, bool COUNT, bool RECORD, bool DARK0, int MATS = 3, int MINW = 3, bool WHITTED = false,
+// render_kernel<ARGS.., CAM> with ARGS' defaults filled in (CAM is the last template parameter)
+template <int CAM, int STACK, bool COUNT, bool RECORD, bool DARK0, int MATS = 3, int MINW = 3, bool WHITTED = false,
           bool COOP = false, bool BIG = false, bool TRACE = false, bool S16 = false>
 struct RenderKernelOf {
-    static constexpr auto fn = &dev::render_kernel<STACK, COUNT, RECORD, DARK0, MATS, MINW, WHITTED, COOP, BIG, TRACE, S16, POSED>;
+    static constexpr auto fn = &dev::render_kernel<STACK, COUNT, RECORD, DARK0, MATS, MINW, WHITTED, COOP, BIG, TRACE, S16, CAM>;
 };
 
-template <int STACK, bool POSED>
-static hipError_t launch_render_t(const RenderArgs& a, const PoseArgs& pose, const LaunchChoice& c, int grid_limit,
-                                  hipStream_t s, hipEvent_t mid) {
+template <int STACK, int CAM>
+static hipError_t launch_render_t(const RenderArgs& a, const PoseArgs& pose, const LensArgs& lens, const LaunchChoice& c,
+                                  int grid_limit, hipStream_t s, hipEvent_t mid) {
     // persistent waves: enough workgroups to fill the chip, each wave loops over work items
     const uint64_t items = dev::render_items(a, ((a.tile_width + 7) / 8) * ((a.tile_height + 7) / 8) * 64);
     const uint64_t want = (items + 255) / 256;
     dim3 grid((unsigned)(want < (uint64_t)grid_limit ? want : (uint64_t)grid_limit)), block(256);
     const bool recording = c.recording, counting = c.counting;
-#define VR_K(...) hipLaunchKernelGGL((RenderKernelOf<POSED, __VA_ARGS__>::fn), grid, block, 0, s, a, a.scene.prims, \
-                                     a.scene.materials, a.scene.bvhs, pose)
+#define VR_K(...) hipLaunchKernelGGL((RenderKernelOf<CAM, __VA_ARGS__>::fn), grid, block, 0, s, a, a.scene.prims, \
+                                     a.scene.materials, a.scene.bvhs, pose, lens)
     if (c.big) {
         // 64-bit load offsets (scenes past 4 GB of triangles or 2^25 wide nodes): the general
         // kernels only (DARK0 = false and every material kind are always correct, only slower), in
@@ -2118,11 +2165,11 @@ static hipError_t launch_render_t(const RenderArgs& a, const PoseArgs& pose, con
     return launch_reduce(a, s, mid);
 }
 
-int launch_block_cull(const RenderArgs& a, const PoseArgs& pose, uint8_t* mask, void* stream) {
+int launch_block_cull(const RenderArgs& a, const PoseArgs& pose, const LensArgs& lens, uint8_t* mask, void* stream) {
     const uint64_t blocks = ((a.tile_width + 7) / 8) * ((a.tile_height + 7) / 8);
     if (blocks == 0) return 0;
     hipLaunchKernelGGL(dev::block_cull_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       a, a.scene.prims, a.scene.bvhs, mask, pose);
+                       a, a.scene.prims, a.scene.bvhs, mask, pose, lens);
     return (int)hipGetLastError();
 }
 
@@ -2140,16 +2187,16 @@ int launch_block_compact(const uint8_t* mask, uint32_t bw, uint32_t bh, bool mor
     return (int)hipGetLastError();
 }
 
-template <bool POSED>
-static hipError_t launch_render_class(int depth, const RenderArgs& a, const PoseArgs& pose, const LaunchChoice& c,
-                                      int grid_limit, hipStream_t s, hipEvent_t mid) {
-    if (depth <= 24) return launch_render_t<24, POSED>(a, pose, c, grid_limit, s, mid);
-    if (depth <= 32) return launch_render_t<32, POSED>(a, pose, c, grid_limit, s, mid);
-    return launch_render_t<48, POSED>(a, pose, c, grid_limit, s, mid);
+template <int CAM>
+static hipError_t launch_render_class(int depth, const RenderArgs& a, const PoseArgs& pose, const LensArgs& lens,
+                                      const LaunchChoice& c, int grid_limit, hipStream_t s, hipEvent_t mid) {
+    if (depth <= 24) return launch_render_t<24, CAM>(a, pose, lens, c, grid_limit, s, mid);
+    if (depth <= 32) return launch_render_t<32, CAM>(a, pose, lens, c, grid_limit, s, mid);
+    return launch_render_t<48, CAM>(a, pose, lens, c, grid_limit, s, mid);
 }
 
-int launch_render(const RenderArgs& a, const PoseArgs& pose, const LaunchChoice& c, int grid_limit, void* stream,
-                  void* mid_event) {
+int launch_render(const RenderArgs& a, const PoseArgs& pose, const LensArgs& lens, const LaunchChoice& c, int grid_limit,
+                  void* stream, void* mid_event) {
     hipStream_t s = (hipStream_t)stream;
     hipEvent_t mid = (hipEvent_t)mid_event;
     if (a.tile_width == 0 || a.tile_height == 0 || a.spp == 0) return 0;
@@ -2158,9 +2205,10 @@ int launch_render(const RenderArgs& a, const PoseArgs& pose, const LaunchChoice&
     // far larger than any whose tree fits the smaller classes; more LDS is only fewer waves)
     const int depth = c.big && c.stack_depth <= 48 ? 48 : c.stack_depth;
     if (depth > 48) return -1000;
-    // RenderArgs::posed: the instantiations whose camera step applies the scene's pose
-    if (a.posed) e = launch_render_class<true>(depth, a, pose, c, grid_limit, s, mid);
-    else e = launch_render_class<false>(depth, a, pose, c, grid_limit, s, mid);
+    // RenderArgs::posed: the instantiations whose camera step applies the scene's pose, or pose and lens
+    if (a.posed == 2) e = launch_render_class<2>(depth, a, pose, lens, c, grid_limit, s, mid);
+    else if (a.posed) e = launch_render_class<1>(depth, a, pose, lens, c, grid_limit, s, mid);
+    else e = launch_render_class<0>(depth, a, pose, lens, c, grid_limit, s, mid);
     return (int)e;
 }
 
@@ -2183,7 +2231,7 @@ int launch_trace_probe(const RenderArgs& a, int stack_depth, int minw, bool s16,
     dim3 g((unsigned)grid), b(256);
 #define VR_KT(ST, MW, S16_)                                                                                    \
     hipLaunchKernelGGL((dev::render_kernel<ST, false, false, true, 3, MW, false, false, false, true, S16_>), g, b, \
-                       0, s, a, a.scene.prims, a.scene.materials, a.scene.bvhs, PoseArgs{})
+                       0, s, a, a.scene.prims, a.scene.materials, a.scene.bvhs, PoseArgs{}, LensArgs{})
     if (stack_depth > 32) return -1000;
     if (s16) {
         if (minw == 3) VR_KT(32, 3, true);

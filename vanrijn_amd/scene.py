@@ -267,14 +267,41 @@ class CameraPose:
     def _from_c(p):
         return CameraPose(*((v.x, v.y, v.z) for v in (p.location, p.right, p.up, p.forward)), p.film_distance)
 
-    def ray(self, width, height, row, column, ux, uy):
+    def ray(self, width, height, row, column, ux, uy, lens=None, lu=0.5, lv=0.5):
         """vr_camera_ray: the camera ray of pixel (row, column) with jitter (ux, uy), on the host from
-        the function the kernels compile: (origin, direction), float64 [3] each."""
+        the function the kernels compile: (origin, direction), float64 [3] each.  With a CameraLens,
+        vr_camera_lens_ray: the ray through the lens point of draws (lu, lv); (0.5, 0.5) is the
+        lens' centre, and a lens of radius 0 gives the pinhole ray."""
         o, d = np.zeros(3), np.zeros(3)
         p = self._c()
+        if lens is not None:
+            cl = lens._c()
+            N.check(N.lib().vr_camera_lens_ray(C.byref(p), C.byref(cl), int(width), int(height), int(row), int(column),
+                                               float(ux), float(uy), float(lu), float(lv),
+                                               o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p)))
+            return o, d
         N.check(N.lib().vr_camera_ray(C.byref(p), int(width), int(height), int(row), int(column), float(ux),
                                       float(uy), o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p)))
         return o, d
+
+
+@dataclass(frozen=True)
+class CameraLens:
+    """vr_camera_lens: a thin lens of radius `lens_radius` ([0, 1e3]; 0 is no lens, the pinhole) in the
+    pose's right / up plane, focused on the plane `focus_distance` ([1e-3, 1e6]) along `forward`."""
+    lens_radius: float = 0.0
+    focus_distance: float = 1.0
+
+    def _c(self):
+        return N.CameraLens(float(self.lens_radius), float(self.focus_distance))
+
+
+def lens_point(lu, lv):
+    """vr_camera_lens_point: the point of the unit disc that lens draws (lu, lv) in [0, 1) map to
+    (Shirley's concentric map with the kernels' fixed sine and cosine): float64 [2]."""
+    out = np.zeros(2)
+    N.check(N.lib().vr_camera_lens_point(float(lu), float(lv), out.ctypes.data_as(C.c_void_p)))
+    return out
 
 
 def look_at(eye, target, up=(0.0, 1.0, 0.0), film_distance=1.0) -> CameraPose:
@@ -567,6 +594,20 @@ class DeviceScene:
         p = N.CameraPose()
         N.check(N.lib().vr_scene_get_camera_pose(self.handle, C.byref(p)))
         return CameraPose._from_c(p)
+
+    def set_camera_lens(self, lens: CameraLens):
+        """vr_scene_set_camera_lens: aperture and focus distance of the camera every render, film, sample
+        and camera-ray call of this scene uses; a radius of 0 turns the lens off.  A lens scene spends
+        draws 2 and 3 of each (pixel, sample) stream on the lens point, so its wavelength is draw 4.
+        The pose is not touched, and set_camera / set_camera_pose leave the lens alone."""
+        cl = lens._c()
+        N.check(N.lib().vr_scene_set_camera_lens(self.handle, C.byref(cl)))
+
+    def camera_lens(self) -> CameraLens:
+        """The scene's lens (vr_scene_get_camera_lens); CameraLens(0, 1) until set_camera_lens."""
+        cl = N.CameraLens()
+        N.check(N.lib().vr_scene_get_camera_lens(self.handle, C.byref(cl)))
+        return CameraLens(cl.lens_radius, cl.focus_distance)
 
     def update_primitives(self, first, prims):
         """vr_scene_update_primitives: replace entries first .. first + len(prims) - 1 of the scene's
