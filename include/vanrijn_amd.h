@@ -43,6 +43,9 @@ extern "C" {
 
 #define VR_ABI_VERSION 10
 #define VR_HAS_FILM 1 /* the vr_film_* entry points below exist (added under ABI 10) */
+/* VR_VARIANT_ONE_BVH, VR_LAUNCH_MULTI_BVH, vr_launch_takes_one_bvh and vr_scene_launch_variant exist
+ * (additions under ABI 10: no structure or existing value changed) */
+#define VR_HAS_ONE_BVH 1
 #define VR_MAX_SPECTRUM_SAMPLES 64
 #define VR_RECURSION_LIMIT 128 /* camera.rs:69 */
 
@@ -515,6 +518,7 @@ typedef struct vr_launch_stats {
 #define VR_VARIANT_COOP 1u         /* the cooperative-tail instantiation (small launches, mirror scenes) */
 #define VR_VARIANT_WIDE_OFFSETS 2u /* the 64-bit-offset kernels (VR_SCENE_WIDE_OFFSETS) */
 #define VR_VARIANT_STACK16 4u      /* 16-bit traversal-stack entries (trees below 65,536 wide nodes; ABI 10) */
+#define VR_VARIANT_ONE_BVH 8u      /* the single-BVH instantiation (one mesh with a wide root; VR_HAS_ONE_BVH) */
 
 #define VR_LAUNCH_TIMED 1u    /* bracket the kernel with HIP events and synchronise at the end */
 #define VR_LAUNCH_COUNTERS 2u /* counting build of the kernel (slower), fills the counters */
@@ -539,6 +543,9 @@ typedef struct vr_launch_stats {
 /* keep 32-bit traversal-stack entries where the tree would allow 16-bit ones: the same records bit for
  * bit; for tests and A/B measurements (ABI 10) */
 #define VR_LAUNCH_STACK32 128u
+/* run the generic kernel (a list of BVHs) where the scene's single BVH would allow the single-BVH
+ * instantiation: the same records bit for bit; for tests and A/B measurements (VR_HAS_ONE_BVH) */
+#define VR_LAUNCH_MULTI_BVH 256u
 
 int vr_render_tile_device(const vr_scene* scene, const vr_render_params* params, double* state, void* stream,
                           uint32_t launch_flags, vr_launch_stats* stats);
@@ -826,6 +833,22 @@ int vr_debug_set_launch_flags(vr_scene* scene, uint32_t flags);
 /* 1 when a scene with this many triangles and 4-wide nodes renders with the 64-bit-offset kernels
  * (VR_SCENE_WIDE_OFFSETS), else 0.  Host only, no device (ABI 8). */
 int vr_scene_needs_wide_offsets(uint64_t triangle_count, uint64_t wide_node_count);
+/* 1 when a launch runs the single-BVH instantiation of the render kernel (VR_VARIANT_ONE_BVH): the
+ * scene's BVH list is one BVH whose 4-wide root `root4` is a node (>= 0: not a one-triangle mesh, not an
+ * empty one), nothing in `other` (VR_CHOICE_* bits of what else the launch selected) excludes it, and
+ * the instantiation exists for the stack class of `stack_depth` entries (16-bit entries: the 24 and 32
+ * classes; 32-bit ones: the 32 class).  The library's own choice, exported for the tests. */
+#define VR_CHOICE_COUNTING 1u     /* VR_LAUNCH_COUNTERS */
+#define VR_CHOICE_RECORD 2u       /* the per-sample record variant (vr_render_samples) */
+#define VR_CHOICE_WHITTED 4u      /* the Whitted integrator's kernel */
+#define VR_CHOICE_COOP_GATED 8u   /* small enough for the cooperative tail, with or without VR_LAUNCH_NO_COOP */
+#define VR_CHOICE_WIDE_OFFSETS 16u /* the 64-bit-offset kernels */
+#define VR_CHOICE_MULTI_BVH 32u   /* VR_LAUNCH_MULTI_BVH */
+int vr_launch_takes_one_bvh(uint64_t bvh_count, int32_t root4, uint32_t other, int32_t stack_depth, int32_t stack16);
+/* The VR_VARIANT_* bits a render of `pixel_samples` (tile pixels x spp) of `scene` with `launch_flags`
+ * would report now (recording: the per-sample record variant).  Launches nothing; host-only scenes too. */
+int vr_scene_launch_variant(const vr_scene* scene, uint64_t pixel_samples, uint32_t launch_flags, int32_t recording,
+                            uint32_t* variant);
 
 int vr_device_count(void);
 const char* vr_last_error(void);

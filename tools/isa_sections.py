@@ -1,11 +1,17 @@
 """Static VALU cost of the render kernel per code section (analysis aid).
 
-Builds vr_render.hip to assembly with -DVR_MARKS (asm ';@mark <name>' comments at the section
-starts of vr_render.hip), takes the C3 kernel (render_kernel<32, false, false, true, 1, 3, false>),
-attributes every instruction to the last marker above it in layout order, and prices each
-instruction with a simple gfx950 issue model (wave64: f32 / int VALU 2 cycles, f64 and 64-bit ops 4,
-f64 transcendentals 16, 32-bit integer multiplies 8).
-    python tools/isa_sections.py [extra hipcc flags]"""
+Builds vr_render.hip to assembly with the product build's flags and -DVR_MARKS (asm ';@mark <name>'
+comments at the section starts of vr_render.hip), takes one instantiation of render_kernel, selected by
+its template arguments, attributes every instruction to the last marker above it in layout order, and
+prices each instruction with a simple gfx950 issue model (wave64: f32 / int VALU 2 cycles, f64 and 64-bit
+ops 4, f64 transcendentals 16, 32-bit integer multiplies 8).  The kernel's resources (VGPRs, SGPRs,
+scratch, LDS, occupancy) are printed first.
+    python tools/isa_sections.py [NAME=VALUE ...] [--asm FILE] [--keep FILE] [other/vr_render.hip] [extra hipcc flags]
+NAME: a template parameter of render_kernel (PARAMS below); the defaults are the C3 timed kernel: STACK 32,
+Lambertian-only, DARK0, 16-bit stack entries, the default camera, the single-BVH instantiation
+(ONE=0: the generic kernel).  --asm: read this assembly (built with -DVR_MARKS) instead of compiling;
+--keep: leave the assembly there.  An older source, whose kernel has fewer template parameters, is
+matched on the parameters it has."""
 import collections
 import os
 import re
@@ -14,10 +20,59 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# the C3 timed kernel: STACK 32, Lambertian-only, DARK0, no Whitted, no cooperative tail (VR_ISA_STACK /
-# VR_ISA_MATS / VR_ISA_COOP=1 pick another instantiation)
-KERNEL = ("_ZN2vr3dev13render_kernelILi%sELb0ELb0ELb1ELi%sELi3ELb0ELb%sELb0EEEvNS_10RenderArgsEPKNS_4PrimEPKNS_8MaterialEPKNS_3BvhE"
-          % (os.environ.get("VR_ISA_STACK", "32"), os.environ.get("VR_ISA_MATS", "1"), os.environ.get("VR_ISA_COOP", "0")))
+# render_kernel's template parameters in order, and the language's defaults of those added over time
+PARAMS = ["STACK", "COUNT", "RECORD", "DARK0", "MATS", "MINW", "WHITTED", "COOP", "BIG", "TRACE", "S16", "CAM", "ONE"]
+DEFAULTS = {"MATS": 3, "MINW": 3, "WHITTED": 0, "COOP": 0, "BIG": 0, "TRACE": 0, "S16": 0, "CAM": 0, "ONE": 0}
+# the C3 timed kernel
+C3 = {"STACK": 32, "COUNT": 0, "RECORD": 0, "DARK0": 1, "MATS": 1, "MINW": 3, "WHITTED": 0, "COOP": 0, "BIG": 0,
+      "TRACE": 0, "S16": 1, "CAM": 0, "ONE": 1}
+
+
+def kernel_args(mangled):
+    """The template arguments of a mangled render_kernel instantiation as a tuple over PARAMS (an older
+    kernel's missing parameters at their defaults), or None for another symbol."""
+    m = re.match(r"_ZN2vr3dev13render_kernelI((?:L[ib]n?\d+E)+)E", mangled)
+    if not m:
+        return None
+    vals = [int(v) for v in re.findall(r"L[ib](\d+)E", m.group(1))]
+    vals += [DEFAULTS[p] for p in PARAMS[len(vals):]]
+    return tuple(vals)
+
+
+def kernel_bodies(text):
+    """{mangled name: instruction lines (markers kept)} of the render_kernel instantiations of an assembly file."""
+    out, name = {}, None
+    for l in text.split("\n"):
+        if name is None:
+            m = re.match(r"(_ZN2vr3dev13render_kernelI\w+):", l)
+            if m:
+                name = m.group(1)
+                out[name] = []
+            continue
+        if l.startswith(".Lfunc_end"):
+            name = None
+            continue
+        t = l.strip()
+        if ";@mark" in t:
+            out[name].append(t)
+            continue
+        t = t.split(";")[0].strip()
+        if not t or t.startswith(".") and not t.endswith(":"):
+            continue
+        out[name].append(t)
+    return out
+
+
+def resources(text, name):
+    """The kernel's metadata: registers, scratch, LDS; and the occupancy the compiler notes below its code."""
+    blk = next(b for b in re.split(r"\n  - ", text.split("amdhsa.kernels:")[1]) if re.search(r"\.name:\s+" + name + r"\s", b))
+    f = {k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1)) for k in
+         ("vgpr_count", "sgpr_count", "sgpr_spill_count", "vgpr_spill_count", "private_segment_fixed_size",
+          "group_segment_fixed_size")}
+    tail = text[text.index("\n" + name + ":"):]
+    occ = re.search(r";\s*Occupancy:\s*(\d+)", tail)
+    f["occupancy"] = int(occ.group(1)) if occ else -1
+    return f
 
 
 def cost(op):
@@ -33,25 +88,49 @@ def cost(op):
 
 
 def main():
-    out = os.path.join(tempfile.mkdtemp(), "render.s")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-           "-fno-fast-math", "--cuda-device-only", "-S", "-DVR_MARKS"] + sys.argv[1:] + \
-          [os.path.join(ROOT, "vanrijn_amd/csrc/vr_render.hip"), "-o", out]
-    subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
-    lines = open(out).read().split("\n")
-    start = next(i for i, l in enumerate(lines) if l.startswith(KERNEL + ":"))
+    argv = sys.argv[1:]
+    want, asm, keep, src = dict(C3), None, None, os.path.join(ROOT, "vanrijn_amd/csrc/vr_render.hip")
+    extra = []
+    while argv:
+        a = argv.pop(0)
+        if re.match(r"[A-Z0-9]+=\d+$", a) and a.split("=")[0] in PARAMS:
+            want[a.split("=")[0]] = int(a.split("=")[1])
+        elif a == "--asm":
+            asm = argv.pop(0)
+        elif a == "--keep":
+            keep = argv.pop(0)
+        elif a.endswith(".hip"):  # another revision's source (e.g. from git archive)
+            src = a
+        else:
+            extra.append(a)
+    if asm is None:
+        asm = keep or os.path.join(tempfile.mkdtemp(), "render.s")
+        # the product build's compile flags (vanrijn_amd/build.py FLAGS): the scheduler options change the code
+        flags = subprocess.check_output([sys.executable, os.path.join(ROOT, "vanrijn_amd/build.py"), "--print-flags"],
+                                        text=True).split()
+        subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["--cuda-device-only", "-S", "-DVR_MARKS"] + extra +
+                              [src, "-o", asm], stderr=subprocess.DEVNULL)
+    text = open(asm).read()
+    bodies = kernel_bodies(text)
+    key = tuple(want[p] for p in PARAMS)
+    names = [n for n in bodies if kernel_args(n) == key]
+    if not names:
+        sys.exit("no render_kernel<%s> in %s" % (", ".join("%s %d" % (p, want[p]) for p in PARAMS), asm))
+    name = names[0]
+    print("render_kernel<%s>" % ", ".join("%s %d" % (p, want[p]) for p in PARAMS))
+    r = resources(text, name)
+    print("vgprs %d  sgprs %d  sgpr spills %d  vgpr spills %d  scratch %d B  lds %d B  occupancy %d" % (
+        r["vgpr_count"], r["sgpr_count"], r["sgpr_spill_count"], r["vgpr_spill_count"], r["private_segment_fixed_size"],
+        r["group_segment_fixed_size"], r["occupancy"]))
     sec = "entry"
     stats = collections.defaultdict(lambda: collections.Counter())
     ops = collections.defaultdict(lambda: collections.Counter())
-    for l in lines[start + 1:]:
-        if l.startswith(".Lfunc_end"):
-            break
-        m = re.search(r";@mark (\w+)", l)
+    for t in bodies[name]:
+        m = re.search(r";@mark (\w+)", t)
         if m:
             sec = m.group(1)
             continue
-        t = l.strip()
-        if not t or t.startswith(";") or t.startswith(".") or t.endswith(":"):
+        if t.endswith(":"):
             continue
         op = t.split()[0]
         st = stats[sec]
@@ -68,6 +147,10 @@ def main():
             st["vmem"] += 1
         if op.startswith("ds_"):
             st["lds"] += 1
+    total = collections.Counter()
+    for st in stats.values():
+        total.update(st)
+    stats["(whole kernel)"] = total
     print("%-14s %6s %6s %6s %6s %7s %5s %5s" % ("section", "insts", "valu", "f64", "salu", "vcycles", "vmem", "lds"))
     for k, st in stats.items():
         print("%-14s %6d %6d %6d %6d %7d %5d %5d" % (k, st["insts"], st["valu"], st["f64"], st["salu"], st["cycles"],

@@ -954,6 +954,8 @@ __device__ __forceinline__ void bsdf_affine(const Material* m, V3 w_o, V3 w_i, d
     }
 }
 
+// ONE: the scene's only BVH owns every triangle hit (render_kernel's ONE instantiations)
+template <bool ONE = false>
 __device__ __forceinline__ void hit_info(const DeviceScene& S, const Best& best, const RayPre& p, HitInfo& h) {
     if (best.kind == kPrim) {
         prim_info(S.prims[best.index], p, best.d, h);
@@ -961,8 +963,12 @@ __device__ __forceinline__ void hit_info(const DeviceScene& S, const Best& best,
         triangle_info(S.tris[best.index], S.normals[best.index], p, best.d, h);
         // material of the owning mesh
         int m = 0;
-        for (int b = 0; b < S.bvh_count; ++b)
-            if (best.object == S.bvhs[b].object) m = S.bvhs[b].material;
+        if constexpr (ONE) {
+            m = S.bvhs[0].material;
+        } else {
+            for (int b = 0; b < S.bvh_count; ++b)
+                if (best.object == S.bvhs[b].object) m = S.bvhs[b].material;
+        }
         h.material = m;
     }
 }

@@ -24,6 +24,58 @@ static bool needs_big_offsets(uint64_t tri_count, uint64_t wide_count) {
     return tri_count * sizeof(vr::TriVerts) >= (1ull << 32) || wide_count >= (1ull << 25);
 }
 
+// The timed render kernels have an instantiation for scenes whose BVH list is one BVH with a wide
+// root (render_kernel<.., ONE>: no list walk, no per-lane BVH cursor; round 8).  `root4`: that BVH's
+// root (negative: a one-triangle mesh, or INT32_MIN for an empty one).  `other`: VR_CHOICE_* bits of
+// what else the launch selected -- the counting, record, Whitted and 64-bit-offset kernels have no such
+// instantiation, VR_LAUNCH_MULTI_BVH asks for the generic kernel, and a launch small enough for the
+// cooperative tail keeps the kernels it had, with the tail or (VR_LAUNCH_NO_COOP) without it, so that
+// flag's A/B still isolates the tail.  It exists with 16-bit stack entries in the 24 and 32 stack classes
+// and with 32-bit ones in the 32 class (vr_render.hip launch_render_t).
+static bool takes_one_bvh(uint64_t bvh_count, int32_t root4, uint32_t other, int stack_depth, bool s16) {
+    if (bvh_count != 1 || root4 < 0 || other != 0) return false;
+    return s16 ? stack_depth <= 32 : (stack_depth > 24 && stack_depth <= 32);
+}
+
+// the launches that may take the cooperative tail: at most VR_COOP_SAMPLES pixel-samples of a DARK0
+// scene with a reflective material (make_args)
+static bool coop_gated(const vr_scene* s, uint64_t pixel_samples) {
+    return pixel_samples <= VR_COOP_SAMPLES && (s->mats & 2) && s->dark0;
+}
+
+// Which render_kernel instantiation a launch of `s` runs.  coop: RenderArgs::coop != 0 (the launch is
+// coop_gated and nothing turned the tail off).  Everything is read from the scene now, so an edit that
+// changed its meshes, materials or tree is reflected at the next launch.
+static vr::LaunchChoice launch_choice(const vr_scene* s, bool coop, bool gated, bool counting, bool recording,
+                                      uint32_t launch_flags) {
+    vr::LaunchChoice lc;
+    // LDS stack entries: the 4-wide walk's, and the binary walk's for Whitted shadow rays
+    const int stack = s->dev.integrator == 1 ? std::max(stack_depth(s), wide_stack_depth(s)) : wide_stack_depth(s);
+    lc.stack_depth = stack;
+    lc.counting = counting;
+    lc.recording = recording;
+    lc.dark0 = s->dark0;
+    lc.mats = s->mats ? s->mats : 3;
+    lc.big = s->force_big || needs_big_offsets(s->tri_count, s->wide_count);
+    // the cooperative tail's instantiations exist for DARK0 scenes with a reflective material
+    lc.coop = coop && !recording && !counting && !lc.big && s->dev.integrator != 1 && s->dark0 && (lc.mats & 2);
+    // 16-bit LDS stack entries: every node index of the tree fits (round 6, vr_render.hip
+    // launch_render_t; VR_LAUNCH_STACK32 keeps 32-bit entries, the same records bit for bit)
+    lc.s16 = !recording && !counting && !lc.big && !lc.coop && s->dev.integrator != 1 && s->wide_count < 65536 &&
+             stack <= 32 && !(launch_flags & VR_LAUNCH_STACK32);
+    const uint32_t other = (counting ? VR_CHOICE_COUNTING : 0u) | (recording ? VR_CHOICE_RECORD : 0u) |
+                           (s->dev.integrator == 1 ? VR_CHOICE_WHITTED : 0u) | (gated || lc.coop ? VR_CHOICE_COOP_GATED : 0u) |
+                           (lc.big ? VR_CHOICE_WIDE_OFFSETS : 0u) |
+                           ((launch_flags & VR_LAUNCH_MULTI_BVH) ? VR_CHOICE_MULTI_BVH : 0u);
+    lc.one_bvh = takes_one_bvh(s->bvhs.size(), s->bvhs.empty() ? INT32_MIN : s->bvhs[0].root4, other, stack, lc.s16);
+    return lc;
+}
+
+static uint32_t variant_bits(const vr::LaunchChoice& lc) {
+    return (lc.coop ? VR_VARIANT_COOP : 0u) | (lc.big ? VR_VARIANT_WIDE_OFFSETS : 0u) |
+           (lc.s16 ? VR_VARIANT_STACK16 : 0u) | (lc.one_bvh ? VR_VARIANT_ONE_BVH : 0u);
+}
+
 // persistent grid: workgroups per CU of the render kernel (3: 3 waves per SIMD); VR_GRID_PER_CU
 // overrides (tuning builds; diagnostic: throughput against occupancy)
 int grid_per_cu() {
@@ -225,7 +277,7 @@ vr::RenderArgs make_args(const vr_scene* s, const vr_render_params* p, double* s
         const uint64_t lsamples = a.tile_width * a.tile_height * (uint64_t)p->spp;
         // (a.coop: the most live paths a wave's tail may have to start it: coop_step serves one or
         // two, lone_walk's whole walks up to four)
-        a.coop = (lsamples <= VR_COOP_SAMPLES && (s->mats & 2) && s->dark0) ? 4u : 0u;
+        a.coop = coop_gated(s, lsamples) ? 4u : 0u;
         if (const char* co = tuning_env("VR_COOP")) a.coop = (uint32_t)std::min(4, std::max(0, atoi(co)));
         a.coop_bounces = VR_COOP_BOUNCES;  // ... once every live path of the wave has bounced this often
         a.lone_walk = 1;
@@ -474,25 +526,9 @@ int enqueue_passes(vr_scene* s, CallCtx* c, const vr_render_params* p, double* s
             if (!start || !mid) return fail(VR_ERROR_DEVICE, "hipEventCreate failed");
             VR_HIP(hipEventRecord(start, st));
         }
-        // LDS stack entries: the 4-wide walk's, and the binary walk's for Whitted shadow rays
-        const int stack = s->dev.integrator == 1 ? std::max(stack_depth(s), wide_stack_depth(s)) : wide_stack_depth(s);
-        vr::LaunchChoice lc;
-        lc.stack_depth = stack;
-        lc.counting = counting;
-        lc.recording = recording;
-        lc.dark0 = s->dark0;
-        lc.mats = s->mats ? s->mats : 3;
-        lc.big = s->force_big || needs_big_offsets(s->tri_count, s->wide_count);
-        // the cooperative tail's instantiations exist for DARK0 scenes with a reflective material
-        lc.coop = a.coop != 0 && !recording && !counting && !lc.big && s->dev.integrator != 1 && s->dark0 &&
-                  (lc.mats & 2);
-        // 16-bit LDS stack entries: every node index of the tree fits (round 6, vr_render.hip
-        // launch_render_t; VR_LAUNCH_STACK32 keeps 32-bit entries, the same records bit for bit)
-        lc.s16 = !recording && !counting && !lc.big && !lc.coop && s->dev.integrator != 1 && s->wide_count < 65536 &&
-                 stack <= 32 && !(launch_flags & VR_LAUNCH_STACK32);
-        if (variant)
-            *variant = (lc.coop ? VR_VARIANT_COOP : 0u) | (lc.big ? VR_VARIANT_WIDE_OFFSETS : 0u) |
-                       (lc.s16 ? VR_VARIANT_STACK16 : 0u);
+        const vr::LaunchChoice lc = launch_choice(s, a.coop != 0, coop_gated(s, a.tile_width * a.tile_height * (uint64_t)q.spp),
+                                                  counting, recording, launch_flags);
+        if (variant) *variant = variant_bits(lc);
         // the COOP instantiations (2 waves per SIMD) keep 3 workgroups per CU (coop_grid_per_cu)
         const int per_cu = lc.coop ? coop_grid_per_cu() : grid_per_cu();
         int lr = vr::launch_render(a, s->pose, s->lens, lc, std::max(1, s->cu_count) * per_cu, st, mid);
@@ -541,6 +577,21 @@ static int sum_pass_times(const std::vector<hipEvent_t>& ev, T* kernel_ms, T* re
 
 int vr_scene_needs_wide_offsets(uint64_t triangle_count, uint64_t wide_node_count) {
     return needs_big_offsets(triangle_count, wide_node_count) ? 1 : 0;
+}
+
+int vr_launch_takes_one_bvh(uint64_t bvh_count, int32_t root4, uint32_t other, int32_t stack_depth, int32_t stack16) {
+    return takes_one_bvh(bvh_count, root4, other, stack_depth, stack16 != 0) ? 1 : 0;
+}
+
+int vr_scene_launch_variant(const vr_scene* s, uint64_t pixel_samples, uint32_t launch_flags, int32_t recording,
+                            uint32_t* variant) {
+    if (!s || !variant) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
+    const bool counting = (launch_flags & VR_LAUNCH_COUNTERS) != 0;
+    launch_flags |= s->debug_launch_flags;
+    const bool gated = coop_gated(s, pixel_samples);
+    *variant = variant_bits(launch_choice(s, gated && !(launch_flags & VR_LAUNCH_NO_COOP), gated, counting, recording != 0,
+                                          launch_flags));
+    return VR_OK;
 }
 
 int vr_render_tile_device(const vr_scene* s, const vr_render_params* p, double* state, void* stream,

@@ -570,10 +570,11 @@ int vr_debug_set_fault_object(vr_scene* s, int32_t object) {
 int vr_debug_set_launch_flags(vr_scene* s, uint32_t flags) {
     if (!s) return fail(VR_ERROR_INVALID_ARGUMENT, "null scene");
     const uint32_t allowed =
-        VR_LAUNCH_NO_CULL | VR_LAUNCH_NO_DIST_CULL | VR_LAUNCH_NO_COOP | VR_LAUNCH_NO_LONE_WALK | VR_LAUNCH_STACK32;
+        VR_LAUNCH_NO_CULL | VR_LAUNCH_NO_DIST_CULL | VR_LAUNCH_NO_COOP | VR_LAUNCH_NO_LONE_WALK | VR_LAUNCH_STACK32 |
+        VR_LAUNCH_MULTI_BVH;
     if (flags & ~allowed)
         return fail(VR_ERROR_INVALID_ARGUMENT,
-                    "only NO_CULL / NO_DIST_CULL / NO_COOP / NO_LONE_WALK / STACK32 apply to every call");
+                    "only NO_CULL / NO_DIST_CULL / NO_COOP / NO_LONE_WALK / STACK32 / MULTI_BVH apply to every call");
     s->debug_launch_flags = flags;
     return VR_OK;
 }

@@ -324,6 +324,7 @@ struct LaunchChoice {
     bool coop;        // the cooperative-tail instantiation (RenderArgs::coop set; never with the above)
     bool big;         // 64-bit node / triangle load offsets (vr_host.cpp needs_big_offsets)
     bool s16;         // 16-bit LDS stack entries (trees below 65,536 wide nodes; timed kernels only)
+    bool one_bvh;     // the single-BVH instantiation (vr_host.cpp takes_one_bvh; timed kernels only)
 };
 int launch_render(const RenderArgs& args, const PoseArgs& pose, const LensArgs& lens, const LaunchChoice& choice,
                   int grid_limit, void* stream, void* mid_event = nullptr);

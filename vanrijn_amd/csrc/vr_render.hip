@@ -234,8 +234,12 @@ __device__ __forceinline__ void lens_camera_ray(const double location[3], double
 // all taken, a pose read in the shared code moved spills and scratch of a dozen instantiations whichever
 // way it was loaded (DESIGN.md section 2 "Camera pose"); the lens keeps its own for the same reason, so
 // the posed ones are what they were before lenses existed ("Camera lens").
+// ONE: the scene has exactly one BVH and its root is a wide node (LaunchChoice::one_bvh; timed kernels
+// only): start_bvhs is straight-line code for S.bvhs[0], phase B has no "next BVH" step, and the
+// current BVH's object is the wave-uniform S.bvhs[0].object instead of a per-lane cursor and copy.
+// With ONE = false the code is what it was before the parameter existed.
 template <int STACK, bool COUNT, bool RECORD, bool DARK0, int MATS = 3, int MINW = 3, bool WHITTED = false,
-          bool COOP = false, bool BIG = false, bool TRACE = false, bool S16 = false, int CAM = 0>
+          bool COOP = false, bool BIG = false, bool TRACE = false, bool S16 = false, int CAM = 0, bool ONE = false>
 // The scene's small uniform tables (planes / spheres, materials, BVH roots) come in again as
 // restrict-qualified arguments: nothing the kernel stores can alias them, so their wave-uniform
 // reads compile to scalar loads (the scalar cache) instead of vector loads through L2.
@@ -344,7 +348,11 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
     Ray32 pre32;
     NodeOrder near_off = {0u, 32u, 64u};  // the ray's near-side quads of a Node4 (set with pre32)
     Best best;
-    int node = -1, sp = 0, bvh_i = 0, cur_object = 0;
+    int node = -1, sp = 0, bvh_i = 0, cur_object = 0;  // (ONE: bvh_i and cur_object are never touched)
+    // the object of the BVH being walked: the lane's copy, or the only BVH's (a scalar).  An expression,
+    // not a lambda: with ONE = false it is `cur_object` to the compiler, and the generic kernels keep
+    // their code instruction for instruction
+#define VR_WALKED_OBJECT (ONE ? S.bvhs[0].object : cur_object)
     int np = 0;  // this lane's queued leaf triangles not yet tested
     // f32 forms of the cull thresholds, widened by the ray's slab margin E (vr_device.h Ray32):
     // cull_far >= bound + margin + E (rounded up), cull_behind <= -behind_margin - E (rounded down;
@@ -411,7 +419,8 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
     };
     auto takes_hit = [&](double d, uint32_t rk) {
         const bool closer = !best.kind | (d < best.d);
-        const bool tie = (d == best.d) & ((best.object == cur_object) ? (rk > best.rank) : (cur_object < best.object));
+        const int co = VR_WALKED_OBJECT;
+        const bool tie = (d == best.d) & ((best.object == co) ? (rk > best.rank) : (co < best.object));
         return closer | tie;
     };
     // a queued leaf: its triangle index, bit 31 set when the leaf's f32 box test was too close to
@@ -443,7 +452,7 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
             best.kind = kTri;
             best.index = tri;
             best.rank = rk;
-            best.object = cur_object;
+            best.object = VR_WALKED_OBJECT;
             set_cull_far();
         }
     };
@@ -530,7 +539,7 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                     best.kind = kTri;
                     best.index = (int)(uint32_t)key;
                     best.rank = rk;
-                    best.object = cur_object;
+                    best.object = VR_WALKED_OBJECT;
                     set_cull_far();
                 }
             }
@@ -541,6 +550,21 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
     };
     // next BVH (from bvh_i) with work; false when the ray is fully traced
     auto start_bvhs = [&]() {
+        if constexpr (ONE) {  // the only BVH, a wide root: the same tests, no list to walk
+            const Bvh& bvh = S.bvhs[0];
+            float flo, fhi;
+            const int rr = slab32(bvh.root_box32, pre32, flo, fhi);
+            if (rr == 0) return false;
+            if (rr == 1) {
+                if (flo > cull_far || fhi < cull_behind) return false;
+            } else {
+                double lo, hi;
+                if (!slab(bvh.root_box, pre, lo, hi) || culled(lo, hi)) return false;
+            }
+            node = bvh.root4;
+            sp = 0;
+            return true;
+        }
         for (; bvh_i < S.bvh_count; ++bvh_i) {
             const Bvh& bvh = S.bvhs[bvh_i];
             if (bvh.root4 == INT32_MIN) continue;
@@ -635,7 +659,7 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
         } else {
             cull_behind = -INFINITY;
         }
-        bvh_i = 0;
+        if constexpr (!ONE) bvh_i = 0;
         node = -1;
         state = start_bvhs() ? kTraversing : kTraversed;
     };
@@ -685,7 +709,7 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
         VR_SEC(3);
         VR_MARK("shade");
         HitInfo h;
-        hit_info(S, best, pre, h);
+        hit_info<ONE>(S, best, pre, h);
         if (COUNT && best.kind == kTri) cnt.shaded++;
         // world_to_bsdf = rows(tangent, cotangent, normal) (algebra_utils.rs:3-5); its
         // determinant via the first-row minors (mat3.rs:106-109)
@@ -1637,14 +1661,19 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
             if (state == kTraversing && node < 0 && np == 0) {
                 VR_SEC(8);
                 VR_MARK("next_bvh");
-                ++bvh_i;
-                if (!start_bvhs()) state = kTraversed;
+                if constexpr (ONE) {
+                    state = kTraversed;  // there is no other BVH
+                } else {
+                    ++bvh_i;
+                    if (!start_bvhs()) state = kTraversed;
+                }
             }
             VR_CP(3);
         } while (lanes_ieq(state, kTraversing) != 0 &&
                  __popcll(lanes_ieq(state, kTraversed)) < (int)A.shade_threshold);
     }
     VR_CP_DUMP();
+#undef VR_WALKED_OBJECT
 #undef VR_CP
 #undef VR_CPN
 #undef VR_CP_PHASE_A
@@ -2074,9 +2103,9 @@ int launch_accumulate(double* state, const double* photons, uint64_t npix, uint3
 
 // render_kernel<ARGS.., CAM> with ARGS' defaults filled in (CAM is the last template parameter)
 template <int CAM, int STACK, bool COUNT, bool RECORD, bool DARK0, int MATS = 3, int MINW = 3, bool WHITTED = false,
-          bool COOP = false, bool BIG = false, bool TRACE = false, bool S16 = false>
+          bool COOP = false, bool BIG = false, bool TRACE = false, bool S16 = false, bool ONE = false>
 struct RenderKernelOf {
-    static constexpr auto fn = &dev::render_kernel<STACK, COUNT, RECORD, DARK0, MATS, MINW, WHITTED, COOP, BIG, TRACE, S16, CAM>;
+    static constexpr auto fn = &dev::render_kernel<STACK, COUNT, RECORD, DARK0, MATS, MINW, WHITTED, COOP, BIG, TRACE, S16, CAM, ONE>;
 };
 
 template <int STACK, int CAM>
@@ -2129,13 +2158,17 @@ static hipError_t launch_render_t(const RenderArgs& a, const PoseArgs& pose, con
     else if (variant == 4) VR_K(STACK, false, false, D, M, 4);  \
     else if (variant == 5 && STACK == 32) VR_K(STACK, false, false, D, M, 4, false, false, false, false, true); \
     else if (variant == 6 && STACK == 32) VR_K(STACK, false, false, D, M, 3, false, false, false, false, true); \
+    else if (s16 && one) VR_K(STACK_S16, false, false, D, M, 3, false, false, false, false, true, true); \
     else if (s16) VR_K(STACK_S16, false, false, D, M, 3, false, false, false, false, true); \
+    else if (one) VR_K(STACK_ONE, false, false, D, M, 3, false, false, false, false, false, true); \
     else VR_K(STACK, false, false, D, M, 3)
 #else
 #define VR_MODES(D, M)                                                                  \
     if (recording) VR_K(STACK, false, true, D, M, 3);                                   \
     else if (counting) VR_K(STACK, true, false, D, M, 3);                               \
+    else if (s16 && one) VR_K(STACK_S16, false, false, D, M, 3, false, false, false, false, true, true); \
     else if (s16) VR_K(STACK_S16, false, false, D, M, 3, false, false, false, false, true); \
+    else if (one) VR_K(STACK_ONE, false, false, D, M, 3, false, false, false, false, false, true); \
     else VR_K(STACK, false, false, D, M, 3)
 #endif
     // the cooperative-tail instantiations: launches the host marks (RenderArgs::coop: small launches
@@ -2149,6 +2182,12 @@ static hipError_t launch_render_t(const RenderArgs& a, const PoseArgs& pose, con
     // 39.22 -> 38.71 ms, 1024^2 @64 10.83 -> 10.58 ms, records bit-identical (profiles/r06/occ)
     constexpr int STACK_S16 = STACK <= 32 ? STACK : 32;  // (never launched for the 48 class)
     const bool s16 = c.s16 && STACK <= 32;
+    // the single-BVH instantiations (LaunchChoice::one_bvh, round 8) of the timed kernels: with 16-bit
+    // stack entries in the 24 and 32 classes, with 32-bit ones in the 32 class only (the host's choice
+    // knows: vr_host.cpp takes_one_bvh; the other classes would add a third to this file's build time
+    // for kernels no scene here runs)
+    constexpr int STACK_ONE = 32;  // (never launched for another class)
+    const bool one = c.one_bvh && (s16 || STACK == 32);
     if (!c.dark0) {
         VR_MODES(false, 3);
     } else if (mats == 1) {

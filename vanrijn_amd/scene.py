@@ -479,19 +479,28 @@ class DeviceScene:
         d["nan_free"] = bool(d["flags"] & N.SCENE_INFO_NAN_FREE)
         return d
 
+    def launch_variant(self, pixel_samples, launch_flags=0, recording=False):
+        """vr_scene_launch_variant: the VARIANT_* bits a render of `pixel_samples` (tile pixels x spp)
+        would report now; launches nothing (host-only scenes too)."""
+        v = C.c_uint32(0)
+        N.check(N.lib().vr_scene_launch_variant(self.handle, int(pixel_samples), int(launch_flags), int(bool(recording)),
+                                                C.byref(v)))
+        return v.value
+
     def set_fault_object(self, obj):
         """Test hook (vr_debug_set_fault_object): hits on scene object `obj` report the singular
         shading basis (VR_ERROR_SINGULAR_BASIS); -1 turns it off."""
         N.check(N.lib().vr_debug_set_fault_object(self.handle, obj))
 
-    def set_launch_flags(self, no_cull=False, no_dist_cull=False, no_coop=False, no_lone_walk=False, stack32=False):
+    def set_launch_flags(self, no_cull=False, no_dist_cull=False, no_coop=False, no_lone_walk=False, stack32=False,
+                         multi_bvh=False):
         """Test hook (vr_debug_set_launch_flags): every later render of this scene -- per-sample
         records and host buffers included -- skips the frustum culling, the BVH distance culling or
-        the cooperative tail or its whole-walk form, or keeps 32-bit traversal-stack entries (each
-        leaves the records bit-identical)."""
+        the cooperative tail or its whole-walk form, keeps 32-bit traversal-stack entries, or runs the
+        generic kernel where the single-BVH one would do (each leaves the records bit-identical)."""
         flags = ((N.LAUNCH_NO_CULL if no_cull else 0) | (N.LAUNCH_NO_DIST_CULL if no_dist_cull else 0) |
                  (N.LAUNCH_NO_COOP if no_coop else 0) | (N.LAUNCH_NO_LONE_WALK if no_lone_walk else 0) |
-                 (N.LAUNCH_STACK32 if stack32 else 0))
+                 (N.LAUNCH_STACK32 if stack32 else 0) | (N.LAUNCH_MULTI_BVH if multi_bvh else 0))
         N.check(N.lib().vr_debug_set_launch_flags(self.handle, flags))
 
     NODE_DTYPE = np.dtype([("box", "<f8", (2, 6)), ("child", "<i4", (2,)), ("pad", "<i4", (6,))])
