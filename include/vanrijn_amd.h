@@ -263,9 +263,11 @@ int vr_scene_update_mesh_device(vr_scene* scene, uint32_t mesh, uint64_t triangl
  *   max y, min z, max z of the four child slots; NaN: empty); int32 child[4] (>= 0 wide node, INT32_MIN
  *   empty, else leaf holding triangle slot ~child); 16 B pad }.
  * vr_scene_triangles: triangle_count records of 80 B each, in slot (traversal leaf) order:
- *   { double v[9]; int64 rank } and { double n[9]; 8 B pad }; a NULL array is skipped.
+ *   { double v[9]; int64 rank } and { double n[9]; int64 material: 0 the owning mesh's, m + 1 material m
+ *   (vr_scene_set_mesh_materials below) }; a NULL array is skipped.
  * vr_scene_bvh_roots: one 96-B record per BVH object, in object order = { double root_box[6];
- *   float root_box32[6]; int32 root, root4, pad, object, tri_base, material }. */
+ *   float root_box32[6]; int32 root, root4, own_materials (1: the mesh's triangles carry materials of their
+ *   own, vr_scene_set_mesh_materials below; else 0), object, tri_base, material }. */
 int vr_scene_wide_nodes(const vr_scene* scene, void* out);
 int vr_scene_triangles(const vr_scene* scene, void* out_verts, void* out_normals);
 int vr_scene_bvh_roots(const vr_scene* scene, void* out);
@@ -348,6 +350,44 @@ int vr_scene_transform_mesh(vr_scene* scene, uint32_t mesh, const double matrix[
 int vr_scene_primitives(const vr_scene* scene, void* out, uint32_t* count);
 int vr_scene_materials(const vr_scene* scene, void* out, uint32_t* count);
 int vr_scene_get_camera(const vr_scene* scene, vr_vec3* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Per-triangle materials: one mesh, one tree, many materials -- an OBJ's usemtl groups rendered
+ * without cutting the model into one mesh per material.  Added under ABI 10 (VR_HAS_MESH_MATERIALS);
+ * no structure and no existing value changes.
+ *
+ * Both setters are scene edits: the contract of "Scene edits" above applies word for word (blocking,
+ *   not thread-safe against other calls on the scene, errors before anything is modified, host
+ *   records only on a VR_SCENE_HOST_ONLY scene, where the device form returns VR_ERROR_HOST_ONLY).
+ * materials[i] is the vr_scene_desc::materials index of INPUT triangle i of mesh `mesh` (the order of
+ *   vr_mesh_desc / vr_scene_update_mesh); NULL goes back to the mesh's single material
+ *   (vr_mesh_desc::material).  Afterwards every entry point (renders, films, samples, vr_integrate_rays*,
+ *   the Whitted shading) answers as though each triangle's material were the given one.
+ * The record: the last 8 bytes of a triangle's 80-B normal record (vr_scene_triangles) are an int64:
+ *   0 means the owning mesh's material -- every record of a scene on which no set call was made, so
+ *   such scenes are unchanged bit for bit -- and m + 1 means material m.  A hit reads the word only where
+ *   the mesh's root record (vr_scene_bvh_roots) has own_materials set, which a set call with an array does
+ *   and the NULL form clears.  Nothing else is written: topology, ranks, trees, extent, VR_SCENE_INFO_NAN_FREE, the kernel choice and the launch variant
+ *   stay.  (The kernel choice and the early stop are derived from ALL of the desc's materials, whichever
+ *   triangle uses which.)
+ * The assignment survives vr_scene_update_mesh[_device] and vr_scene_transform_mesh, the transform's
+ *   base copy included.
+ * VR_ERROR_INVALID_ARGUMENT: a null scene, a bad mesh index, a triangle_count that is not the mesh's, an
+ *   index >= the creation desc's material_count (the device form finds it with a reduction kernel and
+ *   one blocking read-back before it writes).  A NULL array with the mesh's count -- 0 on an empty
+ *   mesh -- is VR_OK.
+ * The device form is ordered after earlier work on `stream` (NULL = the null stream); the host form
+ *   uploads its array and runs the same two kernels.  A mesh's first set call builds its update plan
+ *   (vr_scene_update_mesh above) where it has none; its bytes, and the 4 bytes per triangle the host
+ *   form stages, are added to vr_scene_info::device_bytes.
+ * --------------------------------------------------------------------------------------------- */
+#define VR_HAS_MESH_MATERIALS 1
+int vr_scene_set_mesh_materials(vr_scene* scene, uint32_t mesh, uint64_t triangle_count, const uint32_t* materials);
+int vr_scene_set_mesh_materials_device(vr_scene* scene, uint32_t mesh, uint64_t triangle_count,
+                                       const uint32_t* materials_device, void* stream);
+/* the current assignment in input-triangle order (the mesh's own material where none is set); `out`
+ * holds the mesh's triangle count */
+int vr_scene_mesh_materials(const vr_scene* scene, uint32_t mesh, uint32_t* out);
 
 /* ---------------------------------------------------------------------------------------------
  * Camera pose: where the camera looks and how wide.  The reference's ImageSampler (camera.rs:24-66)
@@ -799,6 +839,16 @@ void vr_colour_xyz_for_wavelength(double wavelength, double out[3]);
  * vr_mesh_free. */
 int vr_load_obj(const char* path, uint64_t* triangle_count, double** vertices, double** normals);
 void vr_mesh_free(double* vertices, double* normals);
+/* vr_load_obj with the file's usemtl groups (VR_HAS_MESH_MATERIALS): triangles, vertices and normals are
+ * exactly vr_load_obj's (the same parse, order and bits); group[t] is the number of the usemtl name in
+ * force at triangle t's face.  Names are numbered in order of first appearance; a repeated name reuses
+ * its number; faces before any usemtl belong to the empty name "", which is in the list only if such
+ * faces exist.  names: one malloc'ed block of group_count NUL-terminated strings, one after the other.
+ * No .mtl file is read: the caller maps names to its own materials (vr_scene_set_mesh_materials).
+ * Free the geometry with vr_mesh_free, group and names with vr_obj_groups_free. */
+int vr_load_obj_groups(const char* path, uint64_t* triangle_count, double** vertices, double** normals,
+                       uint32_t** group, uint32_t* group_count, char** names);
+void vr_obj_groups_free(uint32_t* group, char* names);
 
 /* AccumulationBuffer::to_image_rgb_u8(&ClampingToneMapper) (accumulation_buffer.rs:38-42,
  * image.rs:166-187, colour_xyz.rs:49-84): XYZ -> linear sRGB (the reference's matrix) ->

@@ -189,6 +189,9 @@ SIGNATURES = {
     "vr_scene_update_material": (C.c_int, [_p, _u32, C.POINTER(MaterialDesc)]),
     "vr_scene_set_lights": (C.c_int, [_p, C.POINTER(IntegratorDesc)]),
     "vr_scene_transform_mesh": (C.c_int, [_p, _u32, _p, _p]),
+    "vr_scene_set_mesh_materials": (C.c_int, [_p, _u32, _u64, _p]),
+    "vr_scene_set_mesh_materials_device": (C.c_int, [_p, _u32, _u64, _p, _p]),
+    "vr_scene_mesh_materials": (C.c_int, [_p, _u32, _p]),
     "vr_scene_primitives": (C.c_int, [_p, _p, C.POINTER(C.c_uint32)]),
     "vr_scene_materials": (C.c_int, [_p, _p, C.POINTER(C.c_uint32)]),
     "vr_scene_get_camera": (C.c_int, [_p, C.POINTER(Vec3)]),
@@ -224,6 +227,10 @@ SIGNATURES = {
     "vr_load_obj": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_double)),
                               C.POINTER(C.POINTER(C.c_double))]),
     "vr_mesh_free": (None, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "vr_load_obj_groups": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_double)),
+                                     C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(C.c_uint32)),
+                                     C.POINTER(C.c_uint32), C.POINTER(C.c_void_p)]),
+    "vr_obj_groups_free": (None, [C.POINTER(C.c_uint32), C.c_void_p]),
     "vr_tone_map_device": (C.c_int, [_p, _u64, _p, _i32, _p]),
     "vr_tone_map": (C.c_int, [_p, _u64, _p, _i32]),
     "vr_write_png": (C.c_int, [C.c_char_p, _p, _u32, _u32]),

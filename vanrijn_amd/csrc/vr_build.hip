@@ -180,7 +180,7 @@ __global__ void gather_kernel(const double* verts, const double* norms, const ui
         tn.n[i] = norms[9 * t + i];
     }
     tv.rank = tri_base + (int64_t)pos;  // this build IS the reference topology
-    tn.pad = 0.0;
+    tn.material1 = 0;
     tris[pos] = tv;
     normals[pos] = tn;
 }

@@ -961,13 +961,23 @@ __device__ __forceinline__ void hit_info(const DeviceScene& S, const Best& best,
         prim_info(S.prims[best.index], p, best.d, h);
     } else {
         triangle_info(S.tris[best.index], S.normals[best.index], p, best.d, h);
-        // material of the owning mesh
-        int m = 0;
+        // material of the owning mesh, or the triangle's own (vr_scene_set_mesh_materials: m + 1, one
+        // per lane) where the mesh's record says its triangles carry any: Bvh::own_materials is a scalar
+        // load beside Bvh::material, and a mesh without a table never reads the word
+        int m = 0, own = 0;
         if constexpr (ONE) {
             m = S.bvhs[0].material;
+            own = S.bvhs[0].own_materials;
         } else {
             for (int b = 0; b < S.bvh_count; ++b)
-                if (best.object == S.bvhs[b].object) m = S.bvhs[b].material;
+                if (best.object == S.bvhs[b].object) {
+                    m = S.bvhs[b].material;
+                    own = S.bvhs[b].own_materials;
+                }
+        }
+        if (own) {
+            const int t = (int)S.normals[best.index].material1;
+            m = t ? t - 1 : m;
         }
         h.material = m;
     }

@@ -168,6 +168,7 @@ struct vr_scene {
     bool dark0_materials = true;          // dark0's materials-only part
     std::vector<int> mesh_object;         // the BVH object a mesh backs, or -1
     std::vector<int> mesh_bvh;            // its record in bvhs, or -1
+    std::vector<uint32_t> mesh_material;  // vr_mesh_desc::material (what TriNormals::material1 == 0 stands for)
     std::vector<int32_t> mesh_node_base;  // its first interior node (the root of a mesh of 2 or more triangles)
     std::vector<int32_t> mesh_root4;      // its 4-wide root node, or kEmptyChild
     bool host_stale = false;  // a device update ran: the host copies of trees and triangles are the creation's

@@ -491,3 +491,104 @@ int vr_scene_transform_mesh(vr_scene* s, uint32_t mesh, const double matrix[12],
     return transform_mesh_device(s, mesh, n, a, (hipStream_t)stream);
 }
 
+
+// ------------------------------------------------------------------------------------------
+// Per-triangle materials: TriNormals::material1 of a mesh's slots (0: the mesh's own material,
+// m + 1: material m), scattered through the update plan's slot -> input triangle table.  Nothing
+// else of the scene changes; the transform's base copy, where one exists, takes the same values so
+// that the next transform carries them.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+const char* kMaterialRange = "mesh materials: a material index is out of range";
+
+// Bvh::own_materials of the mesh's root record (a mesh that backs no object has none, and no hit)
+int set_materials_flag(vr_scene* s, uint32_t mi, bool on) {
+    const int bi = s->mesh_bvh[mi];
+    if (bi < 0) return VR_OK;
+    s->bvhs[bi].own_materials = on ? 1 : 0;
+    if (s->host_only) return VR_OK;
+    char* field = (char*)(const_cast<vr::Bvh*>(s->dev.bvhs) + bi) + offsetof(vr::Bvh, own_materials);
+    VR_HIP(hipMemcpy(field, &s->bvhs[bi].own_materials, sizeof(int32_t), hipMemcpyHostToDevice));
+    return VR_OK;
+}
+
+void set_materials_records(vr_scene* s, uint32_t mi, uint64_t n, const uint32_t* mats) {
+    const vr_scene::UpdatePlan& p = s->plans[mi];
+    vr_scene::MeshBase& b = s->bases[mi];
+    const int32_t tri_base = s->mesh_tri_base[mi];
+    for (uint64_t i = 0; i < n; ++i) {
+        const int64_t own = mats ? (int64_t)mats[p.slot_src[i]] + 1 : 0;
+        s->normals[tri_base + i].material1 = own;
+        if (b.normals.size() == n) b.normals[i].material1 = own;
+    }
+}
+
+int set_materials_device(vr_scene* s, uint32_t mi, uint64_t n, const uint32_t* mats, bool device_array, hipStream_t st) {
+    VR_HIP(hipSetDevice(s->device));
+    vr_scene::UpdatePlan& p = s->plans[mi];
+    if (const int rc = build_update_plan(s, mi)) return rc;
+    const uint32_t* d_mats = mats;
+    if (mats && !device_array) {
+        const size_t bytes = (size_t)n * sizeof(uint32_t);
+        if (p.stage_bytes < bytes) {
+            if (p.d_stage) VR_HIP(hipFree(p.d_stage));
+            s->device_bytes -= p.stage_bytes;
+            p.d_stage = nullptr;
+            p.stage_bytes = 0;
+            VR_HIP(hipMalloc(&p.d_stage, bytes));
+            p.stage_bytes = bytes;
+            s->device_bytes += p.stage_bytes;
+        }
+        VR_HIP(hipMemcpyAsync(p.d_stage, mats, bytes, hipMemcpyHostToDevice, st));
+        d_mats = (const uint32_t*)p.d_stage;
+    }
+    if (d_mats) {  // errors come before anything is modified: the largest index is read back first
+        const int e = vr::launch_materials_max(d_mats, n, p.d_valid, st);
+        if (e) return device_fail(e, "mesh materials (validate)");
+        unsigned long long largest = 0;
+        VR_HIP(hipMemcpyAsync(&largest, p.d_valid, sizeof largest, hipMemcpyDeviceToHost, st));
+        VR_HIP(hipStreamSynchronize(st));
+        if (largest >= s->desc_materials) return fail(VR_ERROR_INVALID_ARGUMENT, kMaterialRange);
+    }
+    vr_scene::MeshBase& b = s->bases[mi];
+    vr::TriNormals* base_normals = b.d_base ? (vr::TriNormals*)((char*)b.d_base + (size_t)n * sizeof(vr::TriVerts)) : nullptr;
+    const int e = vr::launch_materials_scatter(d_mats, p.d_slot_src, n,
+                                               const_cast<vr::TriNormals*>(s->dev.normals) + s->mesh_tri_base[mi],
+                                               base_normals, st);
+    if (e) return device_fail(e, "mesh materials (scatter)");
+    VR_HIP(hipStreamSynchronize(st));
+    // the host copy of a host-built scene follows where it is current and the values are at hand
+    if (!s->device_bvh && !s->host_stale && !(mats && device_array))
+        set_materials_records(s, mi, n, mats);
+    else if (!s->device_bvh)
+        s->host_stale = true;
+    return set_materials_flag(s, mi, mats != nullptr);
+}
+
+int set_materials_checked(vr_scene* s, uint32_t mesh, uint64_t n, const uint32_t* mats, bool device_array, void* stream) {
+    if (!s) return fail(VR_ERROR_INVALID_ARGUMENT, "null scene");
+    if (mesh >= s->leaf_order.size()) return fail(VR_ERROR_INVALID_ARGUMENT, "mesh materials: bad mesh index");
+    if (n != s->leaf_order[mesh].size())
+        return fail(VR_ERROR_INVALID_ARGUMENT, "mesh materials: triangle_count differs from the mesh's");
+    if (device_array && s->host_only) return host_only_error();
+    if (mats && !device_array)
+        for (uint64_t t = 0; t < n; ++t)
+            if (mats[t] >= s->desc_materials) return fail(VR_ERROR_INVALID_ARGUMENT, kMaterialRange);
+    if (n == 0) return VR_OK;  // an empty mesh stays empty
+    if (!s->host_only) return set_materials_device(s, mesh, n, mats, device_array, (hipStream_t)stream);
+    if (const int rc = build_update_plan(s, mesh)) return rc;
+    set_materials_records(s, mesh, n, mats);
+    return set_materials_flag(s, mesh, mats != nullptr);
+}
+
+}  // namespace
+
+int vr_scene_set_mesh_materials(vr_scene* s, uint32_t mesh, uint64_t triangle_count, const uint32_t* materials) {
+    return set_materials_checked(s, mesh, triangle_count, materials, false, nullptr);
+}
+
+int vr_scene_set_mesh_materials_device(vr_scene* s, uint32_t mesh, uint64_t triangle_count, const uint32_t* materials_device,
+                                       void* stream) {
+    return set_materials_checked(s, mesh, triangle_count, materials_device, true, stream);
+}

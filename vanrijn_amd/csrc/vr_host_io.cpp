@@ -188,8 +188,10 @@ void vr_colour_xyz_for_wavelength(double wl, double out[3]) {
 // mesh::load_obj (src/mesh.rs:13-88) over the obj 0.9 crate's parsing: "v x y z" and
 // "vn x y z" as f32 (correctly rounded strtof) widened to f64, "f a b c ..." with a, a/t,
 // a//n or a/t/n corners (1-based, negative = relative), fan triangles (v0, v_i, v_{i+1}).
-int vr_load_obj(const char* path, uint64_t* triangle_count, double** vertices, double** normals) {
-    if (!path || !triangle_count || !vertices || !normals) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
+// groups != nullptr (vr_load_obj_groups): per triangle the number of the usemtl name in force at its
+// face, names in order of first appearance ("" for faces before any usemtl, listed only if there are any)
+static int load_obj_impl(const char* path, uint64_t* triangle_count, double** vertices, double** normals,
+                         std::vector<uint32_t>* groups, std::vector<std::string>* names) {
     FILE* f = std::fopen(path, "rb");
     if (!f) return fail(VR_ERROR_IO, std::string("cannot open ") + path);
     std::vector<float> pos, nrm;
@@ -202,6 +204,8 @@ int vr_load_obj(const char* path, uint64_t* triangle_count, double** vertices, d
     char* line = nullptr;
     size_t cap = 0;
     int64_t lineno = 0;
+    int64_t current = -1;  // the group of the faces that follow; -1: the name in force is not numbered yet
+    std::string in_force;  // "" before any usemtl
     // obj 0.9: 1-based indices, negative = relative to the elements read so far, 0 invalid
     auto resolve = [](long long idx, size_t count) -> int64_t {
         if (idx > 0) return (int64_t)idx - 1;
@@ -297,7 +301,23 @@ int vr_load_obj(const char* path, uint64_t* triangle_count, double** vertices, d
                     for (int k = 0; k < 3; ++k) vout.push_back((double)pos[3 * c.v + k]);
                     for (int k = 0; k < 3; ++k) nout.push_back(c.n >= 0 ? (double)nrm[3 * c.n + k] : 0.0);
                 }
+                if (groups) {
+                    if (current < 0) {  // a name is numbered when its first triangle appears
+                        size_t k = 0;
+                        while (k < names->size() && (*names)[k] != in_force) ++k;
+                        if (k == names->size()) names->push_back(in_force);
+                        current = (int64_t)k;
+                    }
+                    groups->push_back((uint32_t)current);
+                }
             }
+        } else if (groups && std::strncmp(s, "usemtl", 6) == 0 && (is_space(s[6]) || s[6] == '\0')) {
+            const char* b = s + 6;
+            while (*b && is_space(*b)) ++b;
+            const char* e = b + std::strlen(b);
+            while (e > b && is_space(e[-1])) --e;
+            in_force.assign(b, e);
+            current = -1;
         }
         // everything else (comments, o, g, s, usemtl, mtllib, l, p, blank lines) carries no
         // geometry for load_obj: objects and groups are flattened in file order (mesh.rs:82-85)
@@ -319,6 +339,48 @@ int vr_load_obj(const char* path, uint64_t* triangle_count, double** vertices, d
     *vertices = v;
     *normals = nn;
     return VR_OK;
+}
+
+int vr_load_obj(const char* path, uint64_t* triangle_count, double** vertices, double** normals) {
+    if (!path || !triangle_count || !vertices || !normals) return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
+    return load_obj_impl(path, triangle_count, vertices, normals, nullptr, nullptr);
+}
+
+int vr_load_obj_groups(const char* path, uint64_t* triangle_count, double** vertices, double** normals, uint32_t** group,
+                       uint32_t* group_count, char** names) {
+    if (!path || !triangle_count || !vertices || !normals || !group || !group_count || !names)
+        return fail(VR_ERROR_INVALID_ARGUMENT, "null argument");
+    std::vector<uint32_t> groups;
+    std::vector<std::string> list;
+    const int rc = load_obj_impl(path, triangle_count, vertices, normals, &groups, &list);
+    if (rc != VR_OK) return rc;
+    if (list.empty()) list.push_back("");  // no triangle at all: still one (empty) name
+    size_t bytes = 0;
+    for (const std::string& n : list) bytes += n.size() + 1;
+    uint32_t* g = (uint32_t*)std::malloc(sizeof(uint32_t) * std::max<size_t>(groups.size(), 1));
+    char* block = (char*)std::malloc(bytes);
+    if (!g || !block) {
+        std::free(g);
+        std::free(block);
+        vr_mesh_free(*vertices, *normals);
+        *vertices = *normals = nullptr;
+        return fail(VR_ERROR_OUT_OF_MEMORY, "group allocation failed");
+    }
+    if (!groups.empty()) std::memcpy(g, groups.data(), sizeof(uint32_t) * groups.size());
+    char* at = block;
+    for (const std::string& n : list) {
+        std::memcpy(at, n.c_str(), n.size() + 1);
+        at += n.size() + 1;
+    }
+    *group = g;
+    *group_count = (uint32_t)list.size();
+    *names = block;
+    return VR_OK;
+}
+
+void vr_obj_groups_free(uint32_t* group, char* names) {
+    std::free(group);
+    std::free(names);
 }
 
 void vr_mesh_free(double* vertices, double* normals) {

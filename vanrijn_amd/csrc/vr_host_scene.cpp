@@ -456,6 +456,7 @@ int vr_scene_create(const vr_scene_desc* desc, int32_t device, uint32_t flags, v
         bvh.tri_base = (int32_t)s->tri_count;
         bvh.material = (int32_t)m.material;
         s->mesh_tri_base[mi] = bvh.tri_base;
+        s->mesh_material.push_back(m.material);
         s->mesh_node_base[mi] = (int32_t)s->node_count;
         if (s->device_bvh) {
             // shape and root box on the host (O(n)); the sort-based build runs after upload
@@ -636,6 +637,38 @@ int vr_scene_triangles(const vr_scene* s, void* out_verts, void* out_normals) {
     const size_t bytes = s->tri_count * sizeof(vr::TriVerts);
     const int rc = dump_rows(s, host_copies_current(s), s->dev.tris, s->tris.data(), bytes, out_verts);
     return rc ? rc : dump_rows(s, host_copies_current(s), s->dev.normals, s->normals.data(), bytes, out_normals);
+}
+
+int vr_scene_mesh_materials(const vr_scene* s, uint32_t mesh, uint32_t* out) {
+    if (!s) return fail(VR_ERROR_INVALID_ARGUMENT, "null scene");
+    if (mesh >= s->leaf_order.size()) return fail(VR_ERROR_INVALID_ARGUMENT, "mesh materials: bad mesh index");
+    const std::vector<uint64_t>& order = s->leaf_order[mesh];
+    const uint64_t n = order.size();
+    if (n == 0) return VR_OK;
+    if (!out) return fail(VR_ERROR_INVALID_ARGUMENT, "mesh materials: null array");
+    const int64_t tri_base = s->mesh_tri_base[mesh];
+    std::vector<vr::TriVerts> tv;
+    std::vector<vr::TriNormals> tn;
+    const vr::TriVerts* tris = s->tris.data() + tri_base;
+    const vr::TriNormals* normals = s->normals.data() + tri_base;
+    if (!host_copies_current(s)) {
+        tv.resize(n);
+        tn.resize(n);
+        VR_HIP(hipSetDevice(s->device));
+        VR_HIP(hipMemcpy(tv.data(), s->dev.tris + tri_base, n * sizeof(vr::TriVerts), hipMemcpyDeviceToHost));
+        VR_HIP(hipMemcpy(tn.data(), s->dev.normals + tri_base, n * sizeof(vr::TriNormals), hipMemcpyDeviceToHost));
+        tris = tv.data();
+        normals = tn.data();
+    }
+    // slot i holds the input triangle at reference leaf position rank - tri_base (build_update_plan's rule)
+    for (uint64_t i = 0; i < n; ++i) {
+        const int64_t r = tris[i].rank - tri_base;
+        if (r < 0 || (uint64_t)r >= n || order[(size_t)r] >= n)
+            return fail(VR_ERROR_DEVICE, "mesh materials: the ranks do not form the mesh's leaf order");
+        const int64_t own = normals[i].material1;
+        out[order[(size_t)r]] = own ? (uint32_t)(own - 1) : s->mesh_material[mesh];
+    }
+    return VR_OK;
 }
 
 int vr_scene_bvh_roots(const vr_scene* s, void* out) {

@@ -65,11 +65,15 @@ struct alignas(16) TriVerts {
 };
 static_assert(sizeof(TriVerts) == 80, "TriVerts must be 80 B");
 
-// Shading normals, same order (read once per closest triangle hit).
+// Shading normals, same order (read once per closest triangle hit).  material1: the triangle's own
+// material (vr_scene_set_mesh_materials): 0 the owning mesh's (every record at creation), m + 1
+// material m.  It shares the record's last 16-B quad with n[8]; the refit's gather and the transform
+// move it through unchanged.
 struct alignas(16) TriNormals {
     double n[9];
-    double pad;
+    int64_t material1;
 };
+static_assert(sizeof(TriNormals) == 80, "TriNormals must be 80 B");
 
 // (vr_scene_materials dumps these rows, vr_scene_primitives the Prim rows below: the sizes are ABI)
 struct Material {
@@ -111,7 +115,9 @@ struct Bvh {
     float root_box32[6];  // the same, rounded outward to f32 (the slab32 pre-test)
     int32_t root;        // >= 0 interior node, < 0 leaf ~triangle, INT32_MIN: empty mesh
     int32_t root4;       // the same in the 4-wide tree (>= 0: Node4 index)
-    int32_t pad_b;
+    // 1: the mesh's triangles carry materials of their own (TriNormals::material1, set by
+    // vr_scene_set_mesh_materials); 0: none does, and a hit does not read the word
+    int32_t own_materials;
     int32_t object;      // scene object index
     int32_t tri_base;    // first triangle of this mesh in the global leaf-ordered arrays
     int32_t material;
@@ -385,6 +391,13 @@ int launch_refit_gather(const double* verts, const double* norms, const uint32_t
 int launch_refit_levels(Node* nodes, Node4* nodes4, const TriVerts* tris, const int32_t* items, const uint32_t* host_first,
                         uint32_t levels, void* stream);
 int launch_refit_root(Bvh* bvh, const Node* nodes, const TriVerts* tris, void* stream);
+// vr_scene_set_mesh_materials.  max: the largest of `n` material indices into *out (zeroed first).
+// scatter: TriNormals::material1 of slot i < n takes materials[slot_src[i]] + 1, or 0 where materials is
+// nullptr (the reset); nothing else of a record is written.  base_normals != nullptr: the transform's
+// base copy takes the same values
+int launch_materials_max(const uint32_t* materials, uint64_t n, unsigned long long* out, void* stream);
+int launch_materials_scatter(const uint32_t* materials, const uint32_t* slot_src, uint64_t n, TriNormals* normals,
+                             TriNormals* base_normals, void* stream);
 // vr_scene_transform_mesh: the Validation of the `n` base records transformed by `a` (vr_refit.h
 // refit::Affine) into out4 (zeroed first), and slot i < n of tris / normals set to the transform of
 // base record i (rank and padding stay)

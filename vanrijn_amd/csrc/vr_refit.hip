@@ -16,6 +16,10 @@
 // vr_scene_transform_mesh runs the same refit after two passes of its own over the mesh's resident
 // base records instead of validate and gather: transform-validate and transform-write.
 //
+// vr_scene_set_mesh_materials has two kernels here beside the gather, whose slot -> input triangle table
+// they share: the largest index of the caller's array (read back before anything is written) and the
+// scatter of material + 1 into the last 8 bytes of the normal records.
+//
 // The per-record arithmetic lives in vr_refit.h, shared with the host refit of VR_SCENE_HOST_ONLY
 // scenes: min / max and outward rounding only, so the stored bits do not depend on who computed them.
 #include <hip/hip_runtime.h>
@@ -75,8 +79,8 @@ __global__ void __launch_bounds__(kBlock) validate_kernel(const double* __restri
 }
 
 // Destination records are 80 B at 16-B alignment: five dwordx4 stores each.  The last quad of a
-// TriVerts holds v[8] and the rank, of a TriNormals n[8] and the padding: rank and padding are read
-// and stored back unchanged.  Source rows are 72 B at 8-B alignment (dwordx2 loads).
+// TriVerts holds v[8] and the rank, of a TriNormals n[8] and the triangle's material word (`pad` below):
+// both are read and stored back unchanged.  Source rows are 72 B at 8-B alignment (dwordx2 loads).
 __global__ void __launch_bounds__(kBlock) gather_kernel(const double* __restrict__ verts, const double* __restrict__ norms,
                                                         const uint32_t* __restrict__ slot_src, uint64_t n,
                                                         TriVerts* tris, TriNormals* normals) {
@@ -146,6 +150,38 @@ __global__ void __launch_bounds__(kBlock) transform_write_kernel(const TriVerts*
     tn[4] = make_double2(nn[8], bn[9]);
 }
 
+// vr_scene_set_mesh_materials: the largest index of the caller's array, reduced as reduce_validation
+// does, so that the host rejects an out-of-range one before anything is written
+__global__ void __launch_bounds__(kBlock) materials_max_kernel(const uint32_t* __restrict__ materials, uint64_t n,
+                                                               unsigned long long* out) {
+    __shared__ uint32_t s_max[kBlock];
+    uint32_t m = 0;
+    for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < n; t += (uint64_t)gridDim.x * kBlock)
+        m = m < materials[t] ? materials[t] : m;
+    s_max[threadIdx.x] = m;
+    __syncthreads();
+    for (int w = kBlock / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w)
+            s_max[threadIdx.x] = s_max[threadIdx.x] < s_max[threadIdx.x + w] ? s_max[threadIdx.x + w] : s_max[threadIdx.x];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) atomicMax(out, (unsigned long long)s_max[0]);
+}
+
+// Slot i takes materials[slot_src[i]] + 1 (materials == nullptr: 0, the mesh's own material).  Only the
+// last 8 bytes of each 80-B record are written, as one aligned double -- the form the gather moves them
+// in; n[0..8] are not touched.  base_normals: the transform's base copy, in the same slot order
+__global__ void __launch_bounds__(kBlock) materials_scatter_kernel(const uint32_t* __restrict__ materials,
+                                                                   const uint32_t* __restrict__ slot_src, uint64_t n,
+                                                                   TriNormals* normals, TriNormals* base_normals) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const long long own = materials ? (long long)materials[slot_src[i]] + 1 : 0;
+    const double bits = __longlong_as_double(own);
+    reinterpret_cast<double*>(normals + i)[9] = bits;
+    if (base_normals) reinterpret_cast<double*>(base_normals + i)[9] = bits;
+}
+
 __global__ void __launch_bounds__(kBlock) refit_level_kernel(Node* nodes, const TriVerts* tris, const int32_t* __restrict__ items,
                                                              uint32_t count) {
     const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
@@ -203,7 +239,26 @@ int launch_transform_write(const TriVerts* base_tris, const TriNormals* base_nor
     return (int)hipGetLastError();
 }
 
-int launch_refit_levels(Node* nodes, Node4* nodes4, const TriVerts* tris, const int32_t* items, const uint32_t* host_first,
+int launch_materials_max(const uint32_t* materials, uint64_t n, unsigned long long* out, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(out, 0, sizeof(unsigned long long), st);
+    if (e != hipSuccess || n == 0) return (int)e;
+    const uint64_t blocks = (n + refit::kBlock - 1) / refit::kBlock;
+    refit::materials_max_kernel<<<dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(refit::kBlock), 0, st>>>(materials, n,
+                                                                                                                 out);
+    return (int)hipGetLastError();
+}
+
+int launch_materials_scatter(const uint32_t* materials, const uint32_t* slot_src, uint64_t n, TriNormals* normals,
+                             TriNormals* base_normals, void* stream) {
+    if (n == 0) return 0;
+    const uint64_t blocks = (n + refit::kBlock - 1) / refit::kBlock;
+    refit::materials_scatter_kernel<<<dim3((unsigned)blocks), dim3(refit::kBlock), 0, (hipStream_t)stream>>>(
+        materials, slot_src, n, normals, base_normals);
+    return (int)hipGetLastError();
+}
+
+int launch_refit_levels(Node* nodes, Node4* nodes4,const TriVerts* tris, const int32_t* items, const uint32_t* host_first,
                         uint32_t levels, void* stream) {
     for (uint32_t l = levels; l-- > 0;) {
         const uint32_t count = host_first[l + 1] - host_first[l];

@@ -174,6 +174,9 @@ class Mesh:
     vertices: np.ndarray
     normals: np.ndarray
     material: object
+    # per-triangle materials, or None: (palette, ids) -- a list of material objects and a uint32 [n]
+    # array of indices into it, in the order of `vertices` (vr_scene_set_mesh_materials)
+    triangle_materials: object = None
 
     def __len__(self):
         return len(self.vertices)
@@ -207,6 +210,35 @@ def load_obj(path, material):
     return Mesh(verts, norms, material)
 
 
+def load_obj_groups(path):
+    """vr_load_obj_groups: load_obj's geometry (the same bits) with the file's usemtl groups:
+    (vertices, normals, group, names) -- group a uint32 [n] array of indices into the list `names`, in
+    order of first appearance; faces before any usemtl belong to the name "".  No .mtl file is read:
+    Mesh(vertices, normals, material, triangle_materials=([materials by name], group)) renders it."""
+    L = N.lib()
+    n, k = C.c_uint64(), C.c_uint32()
+    v = C.POINTER(C.c_double)()
+    nn = C.POINTER(C.c_double)()
+    g = C.POINTER(C.c_uint32)()
+    names = C.c_void_p()
+    N.check(L.vr_load_obj_groups(str(path).encode(), C.byref(n), C.byref(v), C.byref(nn), C.byref(g), C.byref(k),
+                                 C.byref(names)))
+    try:
+        tri = int(n.value)
+        verts = np.ctypeslib.as_array(v, shape=(max(tri * 9, 1),))[:tri * 9].copy().reshape(-1, 3, 3)
+        norms = np.ctypeslib.as_array(nn, shape=(max(tri * 9, 1),))[:tri * 9].copy().reshape(-1, 3, 3)
+        group = np.ctypeslib.as_array(g, shape=(max(tri, 1),))[:tri].copy()
+        out, at = [], names.value
+        for _ in range(k.value):
+            name = C.string_at(at)
+            out.append(name.decode())
+            at += len(name) + 1
+    finally:
+        L.vr_mesh_free(v, nn)
+        L.vr_obj_groups_free(g, names)
+    return verts, norms, group, out
+
+
 # ------------------------------------------------------------------------------ plain-data spec
 @dataclass
 class MaterialSpec:
@@ -230,6 +262,7 @@ class MeshSpec:
     vertices: np.ndarray
     normals: np.ndarray
     material: int
+    triangle_materials: object = None  # uint32 [n] indices into SceneSpec.materials, or None
 
 
 @dataclass
@@ -353,6 +386,13 @@ class Scene:
                     meshes.append(MeshSpec(np.ascontiguousarray(o.mesh.vertices, dtype=np.float64),
                                            np.ascontiguousarray(o.mesh.normals, dtype=np.float64),
                                            mid(o.mesh.material)))
+                    if o.mesh.triangle_materials is not None:
+                        palette, ids = o.mesh.triangle_materials
+                        ids = np.asarray(ids)
+                        if ids.shape != (len(o.mesh.vertices),) or (ids.size and not 0 <= ids.min() <= ids.max() < len(palette)):
+                            raise ValueError("triangle_materials: one palette index per triangle")
+                        scene_ids = np.array([mid(m) for m in palette], dtype=np.uint32)
+                        meshes[-1].triangle_materials = scene_ids[ids.astype(np.int64)] if ids.size else ids.astype(np.uint32)
                     objs.append(ObjectSpec("bvh", mesh=len(meshes) - 1))
                 else:
                     prims = []
@@ -456,6 +496,9 @@ class DeviceScene:
         # __del__ runs; scenes still alive then are released by _release_live_scenes (atexit)
         self._destroy = L.vr_scene_destroy
         _LIVE.add(self)
+        for i, m in enumerate(spec.meshes):  # a MeshSpec from before the field existed has none
+            if getattr(m, "triangle_materials", None) is not None:
+                self.set_mesh_materials(i, m.triangle_materials)
 
     def release(self):
         """vr_scene_destroy now (waits for the scene's queued work); idempotent."""
@@ -536,7 +579,9 @@ class DeviceScene:
 
     def triangles(self):
         """The triangle and normal records in slot (traversal leaf) order (vr_scene_triangles): two
-        structured arrays; `rank` is the scene-wide leaf position in the reference tree."""
+        structured arrays; `rank` is the scene-wide leaf position in the reference tree, and the bytes
+        of the normal records' `pad`, viewed as int64, the triangle's own material: 0 the mesh's, m + 1
+        material m (set_mesh_materials)."""
         n = self.info()["triangle_count"]
         v = np.zeros(n, dtype=self.TRI_VERTS_DTYPE)
         nn = np.zeros(n, dtype=self.TRI_NORMALS_DTYPE)
@@ -546,7 +591,8 @@ class DeviceScene:
         return v, nn
 
     def bvh_roots(self):
-        """One record per BVH object in object order (vr_scene_bvh_roots)."""
+        """One record per BVH object in object order (vr_scene_bvh_roots); `pad` is 1 where the mesh's
+        triangles carry materials of their own (set_mesh_materials), else 0."""
         n = sum(1 for o in self.spec.objects if o.kind == "bvh")
         out = np.zeros(n, dtype=self.BVH_ROOT_DTYPE)
         if n:
@@ -577,6 +623,36 @@ class DeviceScene:
         n = len(self.spec.meshes[mesh].vertices) if 0 <= mesh < len(self.spec.meshes) else 0
         N.check(N.lib().vr_scene_update_mesh_device(self.handle, mesh, n, C.c_void_p(vertices_ptr),
                                                     C.c_void_p(normals_ptr), C.c_void_p(stream_ptr or 0)))
+
+    # ------------------------------------------------------------------ per-triangle materials
+    def set_mesh_materials(self, mesh, ids):
+        """vr_scene_set_mesh_materials: ids[i] is the index into the spec's materials of INPUT triangle
+        i of mesh `mesh` (uint32 [n], n the mesh's triangle count); None goes back to the mesh's single
+        material.  A scene edit: blocks, changes THIS device scene only, and leaves trees, ranks, info()
+        and the launch variant as they are.  The assignment survives update_mesh and transform_mesh."""
+        n = len(self.spec.meshes[mesh].vertices) if 0 <= mesh < len(self.spec.meshes) else 0
+        if ids is None:
+            N.check(N.lib().vr_scene_set_mesh_materials(self.handle, int(mesh), n, None))
+            return
+        a = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        N.check(N.lib().vr_scene_set_mesh_materials(self.handle, int(mesh), a.size, a.ctypes.data_as(C.c_void_p)))
+
+    def set_mesh_materials_device(self, mesh, ptr, stream_ptr=None):
+        """vr_scene_set_mesh_materials_device: as set_mesh_materials, from a device array of the scene's
+        GPU (a raw pointer to n 32-bit indices, e.g. an int32 tensor's data_ptr()), ordered after earlier
+        work on `stream_ptr` (None: the null stream).  An index out of range is found on the device
+        before anything is written."""
+        n = len(self.spec.meshes[mesh].vertices) if 0 <= mesh < len(self.spec.meshes) else 0
+        N.check(N.lib().vr_scene_set_mesh_materials_device(self.handle, int(mesh), n, C.c_void_p(ptr),
+                                                           C.c_void_p(stream_ptr or 0)))
+
+    def mesh_materials(self, mesh):
+        """vr_scene_mesh_materials: the material index of every input triangle of mesh `mesh` now
+        (uint32 [n]; the mesh's own material where none is set)."""
+        n = len(self.spec.meshes[mesh].vertices) if 0 <= mesh < len(self.spec.meshes) else 0
+        out = np.zeros(n, dtype=np.uint32)
+        N.check(N.lib().vr_scene_mesh_materials(self.handle, int(mesh), out.ctypes.data_as(C.c_void_p)))
+        return out
 
     # ------------------------------------------------------------------ scene edits (VR_HAS_SCENE_EDIT)
     # Each changes THIS device scene only and blocks until it is ready; afterwards every call answers
