@@ -68,6 +68,7 @@ __device__ __forceinline__ uint64_t lanes_ine(int a, int b) { return __builtin_a
 __device__ __forceinline__ uint64_t lanes_igt(int a, int b) { return __builtin_amdgcn_sicmp(a, b, 38); }
 __device__ __forceinline__ uint64_t lanes_ige(int a, int b) { return __builtin_amdgcn_sicmp(a, b, 39); }
 __device__ __forceinline__ uint64_t lanes_uge(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, 35); }
+__device__ __forceinline__ uint64_t lanes_ugt(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, 34); }
 __device__ __forceinline__ uint64_t exec_mask() { return __builtin_amdgcn_read_exec(); }
 // set bits of the wave mask m in lanes below this one (two v_mbcnt, no lane-mask registers)
 __device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
@@ -125,6 +126,12 @@ constexpr int kPrioA = kPrio[0], kPrioNode = kPrio[1], kPrioLeaf = kPrio[2];
 #ifndef VR_NODE_STEPS  // node steps per phase-B iteration (round 6: 2)
 #define VR_NODE_STEPS 2
 #endif
+// Round 13's shorter node step and leaf append (DESIGN.md section 6 "Phase-B trims": the leaf votes from one
+// compare per child, raw keys on the 16-bit stack, one test for "takes a step") are in the kernels of one
+// material kind (MATS 1 and 2: the timed kernels of every scene bench.py renders).  The general-material
+// kernels (MATS 3) spill VGPRs to scratch already, and there the same source change only moved the spills,
+// up for some of them: they keep the longer form.
+template <int MATS> constexpr bool kPhaseBTrim = MATS != 3;
 constexpr int kPend = 8;  // FIFO entries per lane of a wave, on average
 constexpr int kWaveList = 64 * kPend;
 static_assert((kWaveList & (kWaveList - 1)) == 0, "the wave FIFO is a power-of-two ring");
@@ -1459,6 +1466,16 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
 #if VR_WATCHDOG  // debug builds: a wave stuck in phase B prints its lanes' state and stops
         uint32_t wd = 0;
 #endif
+        // The lanes that take a node step are those with node >= 0: it implies state == kTraversing.
+        // begin_ray sets node = -1 before start_bvhs gives a lane its root together with kTraversing; a
+        // walk ends with node = -1 (the step's last branch) before next_bvh may leave kTraversing; phase A
+        // only changes lanes that are kTraversed or beyond, whose node has been -1 since.  So the step
+        // guards test node alone.  The COOP kernels keep both tests: their tail hands nodes between lanes.
+        constexpr bool kTrim = kPhaseBTrim<MATS>;
+        constexpr bool kNodeOnly = kTrim && !COOP;
+        auto at_node_lanes = [&]() {
+            return kNodeOnly ? lanes_ige(node, 0) : lanes_ieq(state, kTraversing) & lanes_ige(node, 0);
+        };
         do {
 #if VR_WATCHDOG
             if (++wd > (1u << 20)) {
@@ -1466,6 +1483,7 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                        lane, (int)state, node, sp, (int)np, q_head, q_tail, bvh_i);
                 atomicOr(A.error_flag, 1);
                 state = kDone;
+                node = -1;
                 break;
             }
 #endif
@@ -1475,6 +1493,12 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
             __builtin_amdgcn_s_setprio(kPrioNode);
             // node step (4-wide node), while the wave FIFO has room for four more leaves per lane
             bool lq[4] = {false, false, false, false};  // leaf children this lane queues in this step
+            // ... carried out of the step as the hit child's link (0: no hit), so that the append's one
+            // compare per child gives the vote's lane mask and the branch alike (a bool merged at the end
+            // of the step's branch comes back as a 0 / 1 value that the vote turns into a mask again)
+            // (the kernels that keep the longer form get no variable at all: a dead one moves their spills)
+            typename std::conditional<kTrim, int32_t, const int32_t>::type lqc[4] = {0, 0, 0, 0};
+            typename std::conditional<kTrim, uint64_t, const uint64_t>::type stepm = 0;  // (set per step, below)
             int32_t lent[4];
             bool coop = false;
             if constexpr (COOP) {
@@ -1510,7 +1534,7 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                 }
             }
             if (COUNT) {  // how full this iteration's node step is (the headroom of merging waves)
-                const int n = VR_ROOM ? __popcll(lanes_ieq(state, kTraversing) & lanes_ige(node, 0)) : 0;
+                const int n = VR_ROOM ? __popcll(at_node_lanes()) : 0;
                 if (first_active_lane()) step_hist[n == 0 ? 0 : 1 + (n - 1) / 8]++;
             }
             // VR_NODE_STEPS (2) node steps per iteration: the second, with its leaf append, before the
@@ -1520,13 +1544,26 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
             // profiles/r06/steps/).  The order of node visits and leaf tests changes, the records do not
             // (every step and leaf round is order-independent)
             for (int nst = 0; nst < VR_NODE_STEPS; ++nst) {
+                // kTrim: the lanes that take this step as a lane mask -- one compare for the test whether
+                // any does and for the step's branch
+                if constexpr (kTrim) stepm = (!coop && VR_ROOM) ? at_node_lanes() : 0;
                 if (nst > 0) {
-                    if (coop || (lanes_ieq(state, kTraversing) & lanes_ige(node, 0)) == 0 || !VR_ROOM) break;
+                    if constexpr (kTrim) {
+                        if (stepm == 0) break;
+                    } else {
+                        if (coop || (lanes_ieq(state, kTraversing) & lanes_ige(node, 0)) == 0 || !VR_ROOM) break;
+                    }
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) lq[k] = false;
+                    for (int k = 0; k < 4; ++k) {
+                        lq[k] = false;
+                        if constexpr (kTrim) lqc[k] = 0;
+                    }
                     if (COUNT && first_active_lane()) cnt.trav_slots += 64;
                 }
-                if (!coop && state == kTraversing && node >= 0 && VR_ROOM) {
+                bool takes;
+                if constexpr (kTrim) takes = __builtin_amdgcn_inverse_ballot_w64(stepm);
+                else takes = !coop && state == kTraversing && node >= 0 && VR_ROOM;
+                if (takes) {
                     VR_MARK("node_step");
                     // 32-bit byte offsets from the scalar base (node < 2^25 unless BIG): the loads' saddr form,
                     // no 64-bit address arithmetic per step (load_quads)
@@ -1564,13 +1601,18 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                     // child's node index (A.sort_mask: the low bits, wide enough for every wide node), so
                     // the sorting network is integer min / max and the index rides along; 0xffffffff
                     // (or any key with bit 31 set) marks "not descended".  Only the visiting order depends on the key.
-                    const uint32_t smask = A.sort_mask;
+                    // kTrim: the 16-bit-stack kernels keep exactly 16 index bits, whatever sort_mask says
+                    // (their trees have fewer than 65,536 wide nodes): a push stores the raw key, whose low
+                    // half is the index.
+                    constexpr bool kRawKey = S16 && kTrim;
+                    const uint32_t smask = kRawKey ? 0xffffu : A.sort_mask;
                     uint32_t key[4];
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const bool h = (hm >> k) & 1u;
                         lent[k] = (~c[k]) | (((xm >> k) & 1u) ? INT32_MIN : 0);
-                        lq[k] = h && c[k] < 0;
+                        if constexpr (kTrim) lqc[k] = h ? c[k] : 0;
+                        else lq[k] = h && c[k] < 0;
                         // a leaf or empty child's index is negative: its key has bit 31 set as it is
                         // (negative distances, -0 and negative NaNs clamp to 0 as integers; +inf and
                         // positive NaNs keep bit 31 clear: a hit child is never dropped)
@@ -1598,11 +1640,11 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                             adv[k] = (int32_t)key[k] >> 31;
                             asm volatile("" : "+v"(adv[k]));  // keeps the shift: LLVM would rebuild it as not + shift
                         }
-                        st_node[sp * 256 + tid] = key[3] & smask;
+                        st_node[sp * 256 + tid] = (StackT)(kRawKey ? key[3] : key[3] & smask);
                         sp += 1 + adv[3];
-                        st_node[sp * 256 + tid] = key[2] & smask;
+                        st_node[sp * 256 + tid] = (StackT)(kRawKey ? key[2] : key[2] & smask);
                         sp += 1 + adv[2];
-                        st_node[sp * 256 + tid] = key[1] & smask;
+                        st_node[sp * 256 + tid] = (StackT)(kRawKey ? key[1] : key[1] & smask);
                         sp += 1 + adv[1];
                         node = (int)(key[0] & smask);
                     } else if (sp > 0) {
@@ -1617,7 +1659,14 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                 __builtin_amdgcn_s_setprio(kPrioLeaf);
                 // append this step's leaves to the wave FIFO in (child slot, lane) order (skipped when no
                 // lane met a leaf: main -1.3 %, C5 -4.5 %)
-                const uint64_t lqm[4] = {__ballot(lq[0]), __ballot(lq[1]), __ballot(lq[2]), __ballot(lq[3])};
+                // (a leaf child's link is negative and not the empty slot's INT32_MIN: one unsigned compare,
+                // whose lane mask is the vote -- lanes outside the step carry 0)
+                uint64_t lqm[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    lqm[k] = kTrim ? lanes_ugt((uint32_t)lqc[k], 0x80000000u) : __ballot(lq[k]);
+                    if (kTrim) lq[k] = __builtin_amdgcn_inverse_ballot_w64(lqm[k]);  // the mask itself
+                }
                 if ((lqm[0] | lqm[1] | lqm[2] | lqm[3]) != 0)
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -1627,9 +1676,10 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                         const uint32_t pos = (q_tail + (uint32_t)lanes_below(m)) & (kWaveList - 1);
                         wl_tri[wbase + pos] = lent[k];
                         wl_own[wbase + pos] = (uint8_t)lane;
+                        if (kTrim) ++np;  // (under the branch's mask: one add, no 0 / 1 select)
                     }
                     q_tail += (uint32_t)__popcll(m);
-                    np += lh ? 1 : 0;
+                    if (!kTrim) np += lh ? 1 : 0;
                 }
                 q_tail = __builtin_amdgcn_readfirstlane(q_tail);
             }
@@ -1643,7 +1693,7 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                 // a full round would walk the whole tree unculled
                 const uint64_t trav = lanes_ieq(state, kTraversing);
                 const bool room = VR_ROOM;  // wave-uniform
-                const uint64_t at_node = trav & lanes_ige(node, 0);
+                const uint64_t at_node = kNodeOnly ? lanes_ige(node, 0) : trav & lanes_ige(node, 0);
                 const uint64_t stalled_m = lanes_igt(np, 0) & (room ? ~lanes_ige(node, 0) : exec_mask());
                 const bool few = coop || (tail && __popcll(trav) <= (int)A.leaf_few);
                 if (queued >= A.leaf_threshold || few || __popcll(stalled_m) >= (int)A.leaf_stall ||
