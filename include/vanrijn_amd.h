@@ -815,7 +815,10 @@ int vr_integrate_rays(const vr_scene* scene, uint64_t n, const double* origins, 
 /* update_pixel (accumulation_buffer.rs:44-60, weight 1) of photons[s * pixel_count + p], s = 0 ..
  * spp - 1 in order, into pixel p's record at `state` (the layout of vr_render_tile_device; accumulate
  * 0: from a fresh record, 1: continuing the records there): the render's ordered reduce on its own.
- * Device pointers on `device`, 16-byte aligned; only enqueues on `stream`. */
+ * Device pointers on `device`, 16-byte aligned; only enqueues on `stream`.
+ * Every double is accepted as a wavelength: beyond +-20000 nm, the infinities included, all seven CIE
+ * lobes are +0 as the reference's exp gives them, so the colour is 0 * intensity; a NaN wavelength or
+ * intensity gives NaN in that pixel's sums, as update_pixel does. */
 int vr_accumulate_photons_device(double* state, const vr_photon* photons, uint64_t pixel_count, uint32_t spp,
                                  uint32_t accumulate, int32_t device, void* stream);
 /* ImageSampler::ray_for_pixel (camera.rs:24-66) of the scene's camera for every (sample, pixel) of

@@ -278,16 +278,26 @@ __device__ __forceinline__ double gaussian(double wl, double alpha, double mu, d
 // The ordered reduce's form: exp(-(t^2) * k) with k = 1 / (2 s^2) a compile-time constant per lobe
 // side instead of a division per lobe, and the table-driven exp (vr_exp_table.h, within 2 ulp of
 // exp): the colour is an output value only, within 1e-14 relative of xyz_for_wavelength.
-// `tab` holds VR_EXP_TABLE_INIT (the reduce keeps it in LDS)
+// `tab` holds VR_EXP_TABLE_INIT (the reduce keeps it in LDS).  |wl| <= kLobeReach keeps the argument
+// above -1.6e6, inside vr_exp_tab_near's domain.
 __device__ __forceinline__ double gaussian_kt(double wl, double alpha, double mu, double k1, double k2,
                                               const double* tab) {
     const double k = wl < mu ? k1 : k2;
     const double t = wl - mu;
-    return alpha * vr_exp_tab(-(t * t) * k, tab);
+    return alpha * vr_exp_tab_near(-(t * t) * k, tab);
 }
 #define VR_GT(alpha, mu, s1, s2) \
     gaussian_kt(wl, alpha, mu, 1.0 / (2.0 * ((s1) * (s1))), 1.0 / (2.0 * ((s2) * (s2))), tab)
+// ANY_WL: any double is a wavelength (a caller's photons, vr_accumulate_photons_device).  Beyond
+// +-20000 nm every lobe is exp of less than -85000, +0 in the reference too, so such a wavelength (an
+// infinite one included) is evaluated at +-20000 on its own side of every mu: the same +0 lobes, and
+// the table exp's argument stays finite and in its domain.  One compare per sample instead of one per
+// lobe; NaN fails it and stays NaN; inside, the bits of wl are untouched.  The render's own photons
+// are 0 or 380..740 nm by construction and skip the compare (it measured +0.03 ms on C3's frame).
+constexpr double kLobeReach = 20000.0;
+template <bool ANY_WL>
 __device__ __forceinline__ V3 xyz_for_wavelength_tab(double wl, const double* tab) {
+    if (ANY_WL) wl = fabs(wl) > kLobeReach ? copysign(kLobeReach, wl) : wl;
     return mk(VR_GT(1.056, 599.8, 37.9, 31.0) + VR_GT(0.362, 442.0, 16.0, 26.7) + VR_GT(-0.065, 501.1, 20.4, 26.2),
               VR_GT(0.821, 568.8, 46.9, 40.5) + VR_GT(0.286, 530.9, 16.3, 31.1),
               VR_GT(1.217, 437.0, 11.8, 36.0) + VR_GT(0.681, 459.0, 26.0, 13.8));

@@ -1,9 +1,15 @@
-/* vr_exp_table.h -- exp(x) for x in [-745, 0] by a 64-entry table of 2^(j/64): the ordered reduce's
- * CIE lobes (7 exp per sample).  x = (64 m + j) ln2/64 + r, |r| <= ln2/128 (Cody-Waite with a
- * 36-bit ln2/64, so n * hi is exact for |n| < 2^17); e^r - 1 by its degree-6 Taylor polynomial
- * (truncation < 3e-20); result 2^m * T[j] * (1 + p).  Within 2 ulp of exp (tests/test_exp_table.py
+/* vr_exp_table.h -- exp(x) for x <= 0 by a 64-entry table of 2^(j/64): the ordered reduce's CIE
+ * lobes (7 exp per sample).  x = (64 m + j) ln2/64 + r, |r| <= ln2/128 (Cody-Waite with a 36-bit
+ * ln2/64, so n * hi is exact for |n| < 2^17); e^r - 1 by its degree-6 Taylor polynomial (truncation
+ * < 3e-20); result 2^m * T[j] * (1 + p).  Within 2 ulp of exp on [-745, 0] (tests/test_exp_table.py
  * compiles this header with gcc and checks 10^7 arguments against libm); 13 VALU operations
  * instead of the general exp's 22.  Plain C99 so the test builds it unchanged.
+ *   vr_exp_tab_near(x)  x in [-2^24, 0] or NaN: below the table's range the ldexp underflows to +0
+ *                       exactly as exp does (2^-1075 = e^-745.13..); NaN gives NaN.  Further down n
+ *                       leaves the int range and r grows until the polynomial overflows (inf from
+ *                       about -3.9e68, NaN at -inf): callers keep x inside, as the reduce does for a
+ *                       caller's photons by clamping the wavelength once per sample (vr_device.h).
+ *   vr_exp_tab(x)       every x <= 0, -inf included, and NaN: the same bits on [-1000, 0], +0 below.
  * Table: correctly rounded 2^(j/64), j = 0..63 (decimal arithmetic at 60 digits). */
 #ifndef VR_EXP_TABLE_H
 #define VR_EXP_TABLE_H
@@ -40,7 +46,7 @@
 #define VR_EXP_L_LO 0x1.cf79abc9e3b3ap-46  /* ln2 / 64 - VR_EXP_L_HI */
 
 /* tab: the 64 entries of VR_EXP_TABLE_INIT (wherever the caller keeps them) */
-VR_EXP_FN double vr_exp_tab(double x, const double* tab) {
+VR_EXP_FN double vr_exp_tab_near(double x, const double* tab) {
     const double n = rint(x * VR_EXP_INV_L);
     const int ni = (int)n;
     const double r = fma(-n, VR_EXP_L_LO, fma(-n, VR_EXP_L_HI, x));
@@ -48,6 +54,12 @@ VR_EXP_FN double vr_exp_tab(double x, const double* tab) {
     const double p = fma(r * r, q, r);
     const double t = tab[ni & 63];
     return ldexp(fma(t, p, t), ni >> 6);
+}
+
+/* Any argument: everything below -1000 is evaluated at -1000 (n = -92332, +0 exactly).  A compare
+ * and a select, not fmax: NaN fails the compare and stays NaN. */
+VR_EXP_FN double vr_exp_tab(double x, const double* tab) {
+    return vr_exp_tab_near(x < -1000.0 ? -1000.0 : x, tab);
 }
 
 #endif

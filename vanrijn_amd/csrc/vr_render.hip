@@ -1960,8 +1960,10 @@ __global__ __launch_bounds__(1024) void block_compact_kernel(const uint8_t* mask
 #endif
 typedef double d2 __attribute__((ext_vector_type(2)));
 // accumulation_buffer.rs:44-60 (update_pixel with weight 1.0), one thread per pixel, samples in
-// order: the same Kahan sequence the reference applies call by call.
+// order: the same Kahan sequence the reference applies call by call.  ANY_WL: the photons are a
+// caller's and their wavelengths any doubles (xyz_for_wavelength_tab); false for the render's own.
 __constant__ double c_exp_tab[64] = VR_EXP_TABLE_INIT;
+template <bool ANY_WL>
 __global__ __launch_bounds__(256) void accumulate_kernel(double* state, const double* staging, uint64_t npix,
                                                          uint32_t spp, uint32_t accumulate, const uint8_t* mask,
                                                          uint64_t tile_width, const uint32_t* stage_tag,
@@ -2059,7 +2061,7 @@ __global__ __launch_bounds__(256) void accumulate_kernel(double* state, const do
             for (uint32_t j = 0; j < kB; ++j) {
                 const double wl = v[j].x, I = v[j].y;
                 const double Is = I * 360.0;                     // photon.rs:26-28, camera.rs:121-126
-                const V3 cx = xyz_for_wavelength_tab(wl, etab);  // colour_xyz.rs:31-35
+                const V3 cx = xyz_for_wavelength_tab<ANY_WL>(wl, etab);  // colour_xyz.rs:31-35
                 c[j][0] = cx.x * Is;
                 c[j][1] = cx.y * Is;
                 c[j][2] = cx.z * Is;
@@ -2073,7 +2075,7 @@ __global__ __launch_bounds__(256) void accumulate_kernel(double* state, const do
         const d2 v = __builtin_nontemporal_load(reinterpret_cast<const d2*>(staging) + ((uint64_t)s * npix + p));
         const double wl = v.x, I = v.y;
         const double Is = I * 360.0;
-        const V3 cx = xyz_for_wavelength_tab(wl, etab);
+        const V3 cx = xyz_for_wavelength_tab<ANY_WL>(wl, etab);
         const double c[3] = {cx.x * Is, cx.y * Is, cx.z * Is};
         update(c);
     }
@@ -2130,7 +2132,7 @@ static hipError_t launch_reduce(const RenderArgs& a, hipStream_t s, hipEvent_t m
         if (e != hipSuccess) return e;
     }
     const uint64_t npix = a.tile_width * a.tile_height;
-    hipLaunchKernelGGL(dev::accumulate_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, a.state,
+    hipLaunchKernelGGL(dev::accumulate_kernel<false>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, a.state,
                        (const double*)a.staging, npix, a.spp, a.accumulate, a.block_mask, a.tile_width,
                        a.stage_tag, a.stage_gen, a.error_flag);
     return hipGetLastError();
@@ -2144,7 +2146,7 @@ int launch_accumulate(double* state, const double* photons, uint64_t npix, uint3
     return (int)hipErrorNotSupported;
 #else
     if (npix == 0) return 0;
-    hipLaunchKernelGGL(dev::accumulate_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(dev::accumulate_kernel<true>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        state, photons, npix, spp, accumulate, (const uint8_t*)nullptr, npix,
                        (const uint32_t*)nullptr, 0u, (int32_t*)nullptr);
     return (int)hipGetLastError();
