@@ -212,6 +212,38 @@ def test_stack16_kernels_are_bit_identical(which):
     assert torch.equal(out[0].view(torch.int64), out[1].view(torch.int64))
 
 
+def _mirror_bunny_on_a_plane():
+    """benches/simple_scene.rs's mirror bunny over main.rs's Lambertian plane: both material kinds and nothing
+    else, every colour 0 at 0 nm -- the scenes whose kernels are the MATS = 3, DARK0 ones."""
+    from vanrijn_amd.scene import ColourRgbF, LambertianMaterial, Plane, Scene, Spectrum
+    plane = Plane((0.0, 1.0, 0.0), -2.0, LambertianMaterial(
+        Spectrum.reflection_from_linear_rgb(ColourRgbF.new(0.55, 0.27, 0.04)), 0.1))
+    return Scene(scenes.CAMERA_LOCATION, [[plane], scenes.bench_scene().objects[0]])
+
+
+def test_mixed_material_kernels_are_bit_identical():
+    """A Lambertian and a reflective material together (the MATS = 3, DARK0 kernels), a 16 x 16 tile @2 whose
+    launch is small enough for the cooperative tail: without the tail, the kernel with 32-bit stack entries
+    and the counting kernel leave the records of the one with 16-bit entries, bit for bit; with it, the COOP
+    kernel does.  The launches report which ran."""
+    ds = _mirror_bunny_on_a_plane().device_scene(0)
+    H = W = 128
+    t = Tile(72, 88, 72, 88)  # on the bunny, where paths bounce between it and the plane
+    out = []
+    for kw, variant in (({"coop": False}, N.VARIANT_STACK16), ({"coop": False, "stack16": False}, 0),
+                        ({"coop": False, "counters": True}, 0), ({}, N.VARIANT_COOP)):
+        st = torch.zeros(16 * 16 * 8, dtype=torch.float64, device="cuda")
+        s = render_tile_device(ds, t, H, W, 2, 0x5EED0001, 0, st.data_ptr(), **kw)
+        torch.cuda.synchronize()
+        assert s["variant"] == variant
+        if "counters" in kw:
+            assert s["node_visits"] > 0
+        out.append(st.cpu().view(torch.int64))
+    for o in out[1:]:
+        assert torch.equal(out[0], o)
+    assert np.count_nonzero(out[0].numpy()) > 100
+
+
 def test_stack16_needs_a_small_tree():
     """C5's 1.05 M-triangle mesh has ~413 K wide nodes: its kernels keep 32-bit stack entries."""
     ds = scenes.synthetic_scene().device_scene(0, device_sah=True)

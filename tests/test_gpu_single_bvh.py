@@ -22,7 +22,7 @@ import pytest
 import torch
 
 from camera_pose_checks import poses
-from test_gpu_launch_variants import _decisions_equal, _two_mirror_scene
+from test_gpu_launch_variants import _decisions_equal, _mirror_bunny_on_a_plane, _two_mirror_scene
 from test_gpu_scene_edit import CENTRE, _main_like
 from test_gpu_ties import _tied_scene
 from vanrijn_amd import _native as N
@@ -68,6 +68,29 @@ def test_main_scene_is_bit_identical(case, main_ds):
         a, b = _pair(main_ds, tile, H, W, 4, ONE | S16, S16, more=3 if case == "continued" else 0)
     assert torch.equal(a, b)
     assert np.count_nonzero(a.numpy()) > 1000
+
+
+def test_general_material_kernel_with_a_32_bit_stack_is_bit_identical():
+    """The DARK0 = false kernel's single-BVH instantiation with 32-bit stack entries (the materials scene: a
+    Phong and a glass sphere beside the bunny), a 16 x 16 tile @2 on the bunny."""
+    ds = scenes.materials_scene().device_scene(0)
+    a, b = _pair(ds, Tile(72, 88, 72, 88), 128, 128, 2, ONE, 0, stack16=False)
+    assert torch.equal(a, b)
+    assert np.count_nonzero(a.numpy()) > 100
+
+
+@pytest.mark.parametrize("scene", ["mirror", "mixed"])
+@pytest.mark.parametrize("stack16", [True, False])
+def test_large_launches_of_mirror_scenes_are_bit_identical(scene, stack16):
+    """A scene with a reflective material takes the single-BVH kernels only in a launch too large for the
+    cooperative tail (more than 4 Mi pixel-samples: vr_host.cpp coop_gated), so 512 x 512 @17 here and not a
+    small tile: benches/simple_scene.rs (the reflective-only kernels) and its bunny over a Lambertian plane
+    (the kernels of both kinds), with 16- and with 32-bit stack entries."""
+    ds = (scenes.bench_scene() if scene == "mirror" else _mirror_bunny_on_a_plane()).device_scene(0)
+    s16 = S16 if stack16 else 0
+    a, b = _pair(ds, Tile(0, 512, 0, 512), 512, 512, 17, ONE | s16, s16, stack16=stack16)
+    assert torch.equal(a, b)
+    assert np.count_nonzero(a.numpy()) > 10000
 
 
 def test_debug_flag_forces_the_generic_kernel(main_ds):

@@ -3,26 +3,28 @@
     python tools/isa_diff.py save BEFORE.s     # device assembly of the current source
     python tools/isa_diff.py diff BEFORE.s     # rebuild and list kernels whose instructions differ
     python tools/isa_diff.py files A.s B.s     # compare two assembly files as they are
-Extra hipcc flags may follow the file name.  Comments, directives and labels' names are ignored;
-kernel-argument offsets and register numbers are compared as written.  render_kernel instantiations are
-matched by their template arguments, a file from before a template parameter existed padded with that
-parameter's default (tools/isa_sections.py kernel_args): the "off" instantiations of a new parameter pair
-with the kernels they came from, and the new ones are listed as added."""
+Extra hipcc flags may follow the file name; the others are the product build's (vanrijn_amd/build.py).
+Comments, directives and labels' names are ignored; kernel-argument offsets and register numbers are
+compared as written.  render_kernel instantiations are matched by their template arguments by name
+(tools/isa_sections.py kernel_args): a file from before a parameter existed, or from when the kernel still
+had one that has left, pairs with the same kernels of the other file, and the rest are listed as added or
+missing."""
 import os
 import re
 import subprocess
 import sys
 import tempfile
 
-from isa_sections import kernel_args
+from isa_sections import kernel_args, kernel_label
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
-         "--cuda-device-only", "-S"]
 
 
 def build(out, extra):
-    subprocess.check_call(["/opt/rocm/bin/hipcc"] + FLAGS + extra +
+    # the product build's compile flags (vanrijn_amd/build.py FLAGS): the scheduler options change the code
+    flags = subprocess.check_output([sys.executable, os.path.join(ROOT, "vanrijn_amd/build.py"), "--print-flags"],
+                                    text=True).split()
+    subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["--cuda-device-only", "-S"] + extra +
                           [os.path.join(ROOT, "vanrijn_amd/csrc/vr_render.hip"), "-o", out], stderr=subprocess.DEVNULL)
 
 
@@ -31,8 +33,8 @@ def kernels(path):
     for line in open(path).read().split("\n"):
         m = re.match(r"^([_A-Za-z0-9]+):", line)
         if m and m.group(1).startswith("_ZN2vr3dev"):
-            cur = kernel_args(m.group(1)) or m.group(1)
-            cur = cur if isinstance(cur, str) else "render_kernel<%s>" % ", ".join(str(v) for v in cur)
+            args = kernel_args(m.group(1))
+            cur = kernel_label(args) if args else m.group(1)
             out[cur] = []
             continue
         if cur is None:
@@ -63,10 +65,13 @@ def main():
         if a.get(k) == b.get(k):
             same += 1
         elif k not in a:
-            print("ADDED %-89s %6s instructions" % (k[:89], len(b[k])))
+            print("ADDED %s: %d instructions" % (k, len(b[k])))
+        elif k not in b:
+            print("MISSING %s: %d instructions" % (k, len(a[k])))
         else:
-            print("DIFF %-90s %6s -> %6s instructions" % (k[:90], len(a.get(k, [])), len(b.get(k, []))))
-    print("%d kernels, %d identical, %d added" % (len(set(a) | set(b)), same, len(set(b) - set(a))))
+            print("DIFF %s: %d -> %d instructions" % (k, len(a[k]), len(b[k])))
+    print("%d kernels before, %d after, %d identical, %d added, %d missing" % (
+        len(a), len(b), same, len(set(b) - set(a)), len(set(a) - set(b))))
 
 
 if __name__ == "__main__":

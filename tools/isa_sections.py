@@ -20,23 +20,48 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# render_kernel's template parameters in order, and the language's defaults of those added over time
-PARAMS = ["STACK", "COUNT", "RECORD", "DARK0", "MATS", "MINW", "WHITTED", "COOP", "BIG", "TRACE", "S16", "CAM", "ONE"]
-DEFAULTS = {"MATS": 3, "MINW": 3, "WHITTED": 0, "COOP": 0, "BIG": 0, "TRACE": 0, "S16": 0, "CAM": 0, "ONE": 0}
+# render_kernel's template parameters in order, with the kind of each as a name spells it (i: int, b: bool)
+PARAMS = ["STACK", "COUNT", "RECORD", "DARK0", "MATS", "MINW", "WHITTED", "COOP", "BIG", "S16", "CAM", "ONE"]
+KINDS = "ibbbiibbbbib"
+# ... and of the sources up to round 13, whose kernel had the split probe's TRACE after BIG; a source older
+# still has a prefix of this list (the parameters were added at the end)
+PARAMS_R13 = PARAMS[:9] + ["TRACE"] + PARAMS[9:]
+KINDS_R13 = KINDS[:9] + "b" + KINDS[9:]
+# the language's defaults of the parameters added over time
+DEFAULTS = {"MATS": 3, "MINW": 3, "WHITTED": 0, "COOP": 0, "BIG": 0, "S16": 0, "CAM": 0, "ONE": 0}
 # the C3 timed kernel
 C3 = {"STACK": 32, "COUNT": 0, "RECORD": 0, "DARK0": 1, "MATS": 1, "MINW": 3, "WHITTED": 0, "COOP": 0, "BIG": 0,
-      "TRACE": 0, "S16": 1, "CAM": 0, "ONE": 1}
+      "S16": 1, "CAM": 0, "ONE": 1}
 
 
-def kernel_args(mangled):
-    """The template arguments of a mangled render_kernel instantiation as a tuple over PARAMS (an older
-    kernel's missing parameters at their defaults), or None for another symbol."""
-    m = re.match(r"_ZN2vr3dev13render_kernelI((?:L[ib]n?\d+E)+)E", mangled)
-    if not m:
-        return None
-    vals = [int(v) for v in re.findall(r"L[ib](\d+)E", m.group(1))]
-    vals += [DEFAULTS[p] for p in PARAMS[len(vals):]]
-    return tuple(vals)
+def kernel_args(name):
+    """The template arguments of a render_kernel instantiation by parameter name, or None for another symbol.
+    `name`: the mangled symbol (an assembly file's) or the demangled one (a rocprofv3 trace's).  The kinds of
+    the arguments tell which source the name is from: today's 12, or an older one's (PARAMS_R13 or a prefix
+    of it), whose missing parameters take their defaults and whose TRACE is kept only where it is set, so
+    that a kernel from before the parameter left pairs with the same kernel after."""
+    m = re.match(r"_ZN2vr3dev13render_kernelI((?:L[ib]n?\d+E)+)E", name)
+    if m:
+        found = re.findall(r"L([ib])(\d+)E", m.group(1))
+    else:
+        m = re.search(r"render_kernel<([^<>]*)>", name)
+        if not m:
+            return None
+        found = [("i", v) if v.isdigit() else ("b", str(int(v == "true"))) for v in re.split(r",\s*", m.group(1).strip())]
+    kinds = "".join(k for k, _ in found)
+    names = PARAMS if kinds == KINDS else PARAMS_R13[:len(found)]
+    if names is not PARAMS and kinds != KINDS_R13[:len(found)]:
+        raise ValueError("render_kernel arguments of no known source: " + name)
+    args = dict(DEFAULTS)
+    args.update((p, int(v)) for p, (_, v) in zip(names, found))
+    if not args.get("TRACE"):
+        args.pop("TRACE", None)
+    return args
+
+
+def kernel_label(args):
+    """render_kernel<NAME value, ...> of kernel_args' result: one string per instantiation, for keys and printing"""
+    return "render_kernel<%s>" % ", ".join("%s %d" % (p, args[p]) for p in PARAMS_R13 if p in args)
 
 
 def kernel_bodies(text):
@@ -112,12 +137,11 @@ def main():
                               [src, "-o", asm], stderr=subprocess.DEVNULL)
     text = open(asm).read()
     bodies = kernel_bodies(text)
-    key = tuple(want[p] for p in PARAMS)
-    names = [n for n in bodies if kernel_args(n) == key]
+    names = [n for n in bodies if kernel_args(n) == want]
     if not names:
-        sys.exit("no render_kernel<%s> in %s" % (", ".join("%s %d" % (p, want[p]) for p in PARAMS), asm))
+        sys.exit("no %s in %s" % (kernel_label(want), asm))
     name = names[0]
-    print("render_kernel<%s>" % ", ".join("%s %d" % (p, want[p]) for p in PARAMS))
+    print(kernel_label(want))
     r = resources(text, name)
     print("vgprs %d  sgprs %d  sgpr spills %d  vgpr spills %d  scratch %d B  lds %d B  occupancy %d" % (
         r["vgpr_count"], r["sgpr_count"], r["sgpr_spill_count"], r["vgpr_spill_count"], r["private_segment_fixed_size"],

@@ -18,15 +18,15 @@ import json
 import os
 import sys
 
+from isa_sections import kernel_args
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def is_timed_render(name):
-    # render_kernel<STACK, COUNT, RECORD, ...>: the timed launches have COUNT = false
-    if "render_kernel<" not in name:
-        return False
-    targs = name.split("render_kernel<")[1].split(">")[0].split(",")
-    return targs[1].strip() == "false" and targs[2].strip() == "false"
+    # the timed launches of render_kernel are neither the counting nor the recording kernel
+    args = kernel_args(name)
+    return args is not None and not args["COUNT"] and not args["RECORD"]
 
 
 def load(pass_dir):

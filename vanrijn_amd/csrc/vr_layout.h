@@ -5,6 +5,7 @@
 // reads whole is a multiple of 16 B and 16-B aligned so it is fetched with dwordx4 loads.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 namespace vr {
@@ -223,16 +224,9 @@ struct RenderArgs {
     // nullptr: every block of the tile is live
     const uint32_t* live_blocks;
     const uint32_t* live_count;
+    uint64_t reserved[4];  // unused: keeps the kernel-argument offsets of the members below (moving them moves spills)
     // debug builds only (-DVR_STAGE_GUARD, DESIGN.md section 8 "staging invariant"): beside every
     // staged photon the launch's generation, which the ordered reduce checks before reading it
-    // analysis builds only (-DVR_SPLIT_PROBE, DESIGN.md section 6 "the megakernel split"): the render
-    // kernel appends every traced ray (6 f64) to probe_rays (probe_count: the next slot; at most
-    // probe_n); the TRACE kernel reads probe_n rays from it and writes their closest hits (2 f64
-    // each) to probe_hits
-    const double* probe_rays;
-    double* probe_hits;
-    unsigned long long* probe_count;
-    uint64_t probe_n;
     uint32_t* stage_tag;  // [pass sample][tile pixel], or nullptr
     uint32_t stage_gen;   // this pass's generation (never 0)
     // 1: the scene's pose is not the default one and the camera step loads it (vr_render.hip
@@ -240,6 +234,9 @@ struct RenderArgs {
     // 2: the scene has a lens (lens_radius != 0) and the step applies pose and lens, whatever the pose
     uint32_t posed;
 };
+// the kernel-argument offsets the render kernel's register allocation was measured with (`reserved` above)
+static_assert(offsetof(RenderArgs, posed) == 460, "RenderArgs: a member moved");
+static_assert(sizeof(RenderArgs) == 464, "RenderArgs: its size changed");
 
 struct TraceArgs {
     DeviceScene scene;
@@ -408,9 +405,6 @@ int launch_transform_validate(const TriVerts* base_tris, const TriNormals* base_
                               const refit::Affine& a, unsigned long long* out4, void* stream);
 int launch_transform_write(const TriVerts* base_tris, const TriNormals* base_normals, uint64_t n, const refit::Affine& a,
                            TriVerts* tris, TriNormals* normals, void* stream);
-#ifdef VR_SPLIT_PROBE  // analysis builds (vr_render.hip)
-int launch_trace_probe(const RenderArgs& args, int stack_depth, int minw, bool s16, int grid, void* stream);
-#endif
 const char* device_error_string(int code);
 
 }  // namespace vr

@@ -120,9 +120,6 @@ __host__ __device__ inline uint64_t render_items(const RenderArgs& a, uint64_t p
 #endif
 constexpr int kPrio[3] = {VR_PRIO};
 constexpr int kPrioA = kPrio[0], kPrioNode = kPrio[1], kPrioLeaf = kPrio[2];
-#ifndef VR_WATCHDOG  // debug builds: a wave stuck in phase B prints its lanes' state and stops
-#define VR_WATCHDOG 0
-#endif
 #ifndef VR_NODE_STEPS  // node steps per phase-B iteration (round 6: 2)
 #define VR_NODE_STEPS 2
 #endif
@@ -229,10 +226,6 @@ __device__ __forceinline__ void lens_camera_ray(const double location[3], double
 // BIG: 64-bit byte offsets for the node and triangle loads -- scenes whose triangle array reaches 4 GB
 // (53.7 M triangles) or whose 4-wide tree has 2^25 nodes (vr_host.cpp needs_big_offsets); every other
 // scene's kernels address both arrays with 32-bit offsets from the scalar base (the loads' saddr form)
-// TRACE (analysis builds, -DVR_SPLIT_PROBE: DESIGN.md section 6, "the megakernel split"): the same
-// kernel as a traversal-only pass over a buffer of rays -- work items are rays (RenderArgs::probe_rays,
-// 6 f64 each), phase A stores each closest hit (probe_hits, 2 f64: distance, kind | index << 2 and
-// object) instead of shading, and no path state exists, so the register peak is traversal's alone.
 // S16: 16-bit LDS stack entries (trees below 65,536 wide nodes): half the stack's LDS, so more
 // workgroups fit a CU.
 // CAM: the camera step's mode (RenderArgs::posed): 0 the default pose, 1 the scene's pose, 2 the scene's
@@ -246,7 +239,7 @@ __device__ __forceinline__ void lens_camera_ray(const double location[3], double
 // current BVH's object is the wave-uniform S.bvhs[0].object instead of a per-lane cursor and copy.
 // With ONE = false the code is what it was before the parameter existed.
 template <int STACK, bool COUNT, bool RECORD, bool DARK0, int MATS = 3, int MINW = 3, bool WHITTED = false,
-          bool COOP = false, bool BIG = false, bool TRACE = false, bool S16 = false, int CAM = 0, bool ONE = false>
+          bool COOP = false, bool BIG = false, bool S16 = false, int CAM = 0, bool ONE = false>
 // The scene's small uniform tables (planes / spheres, materials, BVH roots) come in again as
 // restrict-qualified arguments: nothing the kernel stores can alias them, so their wave-uniform
 // reads compile to scalar loads (the scalar cache) instead of vector loads through L2.
@@ -600,20 +593,6 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
     // there, not in registers of its own that would stay live through the traversal phase):
     // primitive lists first, then the BVHs
     auto begin_ray = [&]() {
-#ifdef VR_SPLIT_PROBE  // analysis builds: every traced ray's (origin, direction) into probe_rays
-        if (!TRACE && A.probe_rays) {
-            const uint64_t m = exec_mask();
-            const unsigned leader = (unsigned)__builtin_ctzll(m);
-            unsigned long long b = 0;
-            if (lane == leader) b = atomicAdd(A.probe_count, (unsigned long long)__popcll(m));
-            const uint64_t slot = uniform64(__shfl(b, (int)leader)) + lanes_below(m);
-            if (slot < A.probe_n) {
-                double* r = const_cast<double*>(A.probe_rays) + 6 * slot;
-                r[0] = pre.o.x; r[1] = pre.o.y; r[2] = pre.o.z;
-                r[3] = pre.d.x; r[4] = pre.d.y; r[5] = pre.d.z;
-            }
-        }
-#endif
         pre = prepare(Ray{pre.o, pre.d});
         pre32 = prepare32(pre, S.extent);
         near_off = node_near_offsets(pre32);
@@ -1253,16 +1232,7 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
             // lanes still traverse: the deferred lanes wait (state kTraversed) and the next phase
             // A shades them with more lanes busy (misses are finished at once either way)
             bool shade_now = true, finish_now = true;
-            if constexpr (TRACE) {
-                if (state == kTraversed) {  // the ray's closest hit, then the next ray
-                    double* h = A.probe_hits + 2 * (uint64_t)px;
-                    __builtin_nontemporal_store(best.d, &h[0]);
-                    __builtin_nontemporal_store(__longlong_as_double(
-                        (long long)(((uint64_t)(uint32_t)best.object << 32) | ((uint32_t)best.index << 2) | (uint32_t)best.kind)), &h[1]);
-                    ++s_idx;
-                    state = kNeedRay;
-                }
-            } else if (A.shade_min | A.miss_min) {
+            if (A.shade_min | A.miss_min) {
                 const bool idle = lanes_ieq(state, kTraversing) == 0;
                 const uint64_t done_trav = lanes_ieq(state, kTraversed);
                 const int nhit = __popcll(done_trav & lanes_ine((int)best.kind, (int)kNone));
@@ -1270,22 +1240,12 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                 shade_now = nhit >= (int)A.shade_min || idle;
                 finish_now = nmiss >= (int)A.miss_min || idle;
             }
-            if (!TRACE && state == kTraversed && (best.kind == kNone ? finish_now : shade_now)) {
+            if (state == kTraversed && (best.kind == kNone ? finish_now : shade_now)) {
                 VR_MARK("traversed");
                 // one call site for shade(): two inlined copies would both run whenever a wave
                 // holds camera-ray hits and bounce hits at once
                 bool go = false;
                 fin = false;
-#ifdef VR_DEBUG_PIX  // debug builds: one sample's traced rays and closest hits, for tools/debug_path.py
-                if ((A.start_row + py) * A.width + (A.start_column + px) == (uint64_t)VR_DEBUG_PIX &&
-                    A.first_sample + s_idx == (uint64_t)VR_DEBUG_SMP)
-                    printf("vrdbg %d %d %d %llx %llx %llx %llx %llx %llx %llx %d\n", depth, (int)best.kind, best.index,
-                           (unsigned long long)__double_as_longlong(best.d),
-                           (unsigned long long)__double_as_longlong(pre.o.x), (unsigned long long)__double_as_longlong(pre.o.y),
-                           (unsigned long long)__double_as_longlong(pre.o.z), (unsigned long long)__double_as_longlong(pre.d.x),
-                           (unsigned long long)__double_as_longlong(pre.d.y), (unsigned long long)__double_as_longlong(pre.d.z),
-                           best.kind == kTri ? (int)best.rank : -1);
-#endif
                 if (WHITTED && depth >= 0) {
                     if (!best.kind) {
                         finish(lambda, Acc);  // the continuation missed: photon.scale_intensity(0)
@@ -1352,16 +1312,7 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                     const uint64_t want = (uint64_t)__popcll(m);
                     w_next = uniform64(w_next + (want < avail ? want : avail));
                 }
-                if (TRACE && take) {  // a work item is one ray of probe_rays
-                    const uint64_t g = base + rank;
-                    if (g >= A.probe_n) {
-                        state = kDone;
-                    } else {
-                        px = (uint32_t)g;
-                        s_idx = 0;
-                        s_end = 1;
-                    }
-                } else if (take) {
+                if (take) {
                     const uint64_t g = base + rank;
                     if (g >= items) {
                         state = kDone;
@@ -1412,14 +1363,7 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                 }
             }
             VR_STAMP(1);
-            if (TRACE && state == kNeedRay) {
-                const double* r = A.probe_rays + 6 * (uint64_t)px;
-                pre.o = mk(__builtin_nontemporal_load(&r[0]), __builtin_nontemporal_load(&r[1]),
-                           __builtin_nontemporal_load(&r[2]));
-                pre.d = mk(__builtin_nontemporal_load(&r[3]), __builtin_nontemporal_load(&r[4]),
-                           __builtin_nontemporal_load(&r[5]));
-                state = kRayReady;
-            } else if (state == kNeedRay) {
+            if (state == kNeedRay) {
                 const uint64_t row = A.start_row + py, col = A.start_column + px;
                 rng.reset(stream_base_keyed(A.seed_key, row * A.width + col, A.first_sample + s_idx));
                 // ImageSampler (camera.rs:24-66): film (w/h, 1) or (1, w/h); x's draw first
@@ -1463,9 +1407,6 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
         (void)tail;
         VR_CP(0);
         // ---------------------------------------------------------------- phase B: traverse
-#if VR_WATCHDOG  // debug builds: a wave stuck in phase B prints its lanes' state and stops
-        uint32_t wd = 0;
-#endif
         // The lanes that take a node step are those with node >= 0: it implies state == kTraversing.
         // begin_ray sets node = -1 before start_bvhs gives a lane its root together with kTraversing; a
         // walk ends with node = -1 (the step's last branch) before next_bvh may leave kTraversing; phase A
@@ -1477,16 +1418,6 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
             return kNodeOnly ? lanes_ige(node, 0) : lanes_ieq(state, kTraversing) & lanes_ige(node, 0);
         };
         do {
-#if VR_WATCHDOG
-            if (++wd > (1u << 20)) {
-                printf("vr watchdog: block %u lane %u state %d node %d sp %d np %d q %u..%u bvh %d\n", blockIdx.x,
-                       lane, (int)state, node, sp, (int)np, q_head, q_tail, bvh_i);
-                atomicOr(A.error_flag, 1);
-                state = kDone;
-                node = -1;
-                break;
-            }
-#endif
             if (COUNT && first_active_lane()) cnt.trav_slots += 64;
             VR_STAMP(5);
             VR_MARK("phaseB_top");
@@ -2153,12 +2084,26 @@ int launch_accumulate(double* state, const double* photons, uint64_t npix, uint3
 #endif
 }
 
-// render_kernel<ARGS.., CAM> with ARGS' defaults filled in (CAM is the last template parameter)
-template <int CAM, int STACK, bool COUNT, bool RECORD, bool DARK0, int MATS = 3, int MINW = 3, bool WHITTED = false,
-          bool COOP = false, bool BIG = false, bool TRACE = false, bool S16 = false, bool ONE = false>
-struct RenderKernelOf {
-    static constexpr auto fn = &dev::render_kernel<STACK, COUNT, RECORD, DARK0, MATS, MINW, WHITTED, COOP, BIG, TRACE, S16, CAM, ONE>;
+// One instantiation of render_kernel, named by field; the defaults are the template's
+struct Variant {
+    int stack = 0;
+    bool count = false, record = false, dark0 = false;
+    int mats = 3, minw = 3;
+    bool whitted = false, coop = false, big = false, s16 = false;
+    int cam = 0;
+    bool one = false;
 };
+
+// Launches the instantiation that `make`, a captureless constexpr lambda, returns: the one place that
+// spells render_kernel's template arguments in their order
+template <class Make>
+static void launch_variant(Make make, dim3 grid, hipStream_t s, const RenderArgs& a, const PoseArgs& pose,
+                           const LensArgs& lens) {
+    constexpr Variant v = make();
+    hipLaunchKernelGGL((dev::render_kernel<v.stack, v.count, v.record, v.dark0, v.mats, v.minw, v.whitted, v.coop, v.big,
+                                           v.s16, v.cam, v.one>),
+                       grid, dim3(256), 0, s, a, a.scene.prims, a.scene.materials, a.scene.bvhs, pose, lens);
+}
 
 template <int STACK, int CAM>
 static hipError_t launch_render_t(const RenderArgs& a, const PoseArgs& pose, const LensArgs& lens, const LaunchChoice& c,
@@ -2166,62 +2111,70 @@ static hipError_t launch_render_t(const RenderArgs& a, const PoseArgs& pose, con
     // persistent waves: enough workgroups to fill the chip, each wave loops over work items
     const uint64_t items = dev::render_items(a, ((a.tile_width + 7) / 8) * ((a.tile_height + 7) / 8) * 64);
     const uint64_t want = (items + 255) / 256;
-    dim3 grid((unsigned)(want < (uint64_t)grid_limit ? want : (uint64_t)grid_limit)), block(256);
+    const dim3 grid((unsigned)(want < (uint64_t)grid_limit ? want : (uint64_t)grid_limit));
     const bool recording = c.recording, counting = c.counting;
-#define VR_K(...) hipLaunchKernelGGL((RenderKernelOf<CAM, __VA_ARGS__>::fn), grid, block, 0, s, a, a.scene.prims, \
-                                     a.scene.materials, a.scene.bvhs, pose, lens)
+    // VR_K(v.field = value, ...): the kernel of this stack class and camera mode with those fields set
+#define VR_K(...)                             \
+    launch_variant(                           \
+        []() constexpr {                      \
+            Variant v;                        \
+            v.stack = STACK, v.cam = CAM;     \
+            __VA_ARGS__;                      \
+            return v;                         \
+        },                                    \
+        grid, s, a, pose, lens)
+    // ... its recording, counting or timed kernel, as the launch asks
+#define VR_MODES(...)                                          \
+    if (recording) VR_K(v.record = true, __VA_ARGS__);         \
+    else if (counting) VR_K(v.count = true, __VA_ARGS__);      \
+    else VR_K(__VA_ARGS__)
+#ifdef VR_TUNING_VARIANTS  // experiment hooks of tuning builds only (tools/variants.py)
+    // 1..4 = force that many waves per SIMD (default 3); 5 / 6: 16-bit LDS stack entries (trees below
+    // 65,536 wide nodes only) at 4 / 3 waves per SIMD; VR_FORCE_MATS (below): the material specialisation
+    const char* ve = getenv("VR_KERNEL_VARIANT");
+    const int variant = ve ? atoi(ve) : 0;
+#define VR_TUNING_ARMS(...)                                                                  \
+    else if (variant == 1) VR_K(v.minw = 1, __VA_ARGS__);                                    \
+    else if (variant == 2) VR_K(v.minw = 2, __VA_ARGS__);                                    \
+    else if (variant == 4) VR_K(v.minw = 4, __VA_ARGS__);                                    \
+    else if (variant == 5 && STACK == 32) VR_K(v.minw = 4, v.s16 = true, __VA_ARGS__);       \
+    else if (variant == 6 && STACK == 32) VR_K(v.s16 = true, __VA_ARGS__);
+#else
+#define VR_TUNING_ARMS(...)
+#endif
+    // ... where the timed kernel is the one with 16-bit stack entries, the single-BVH one, both or neither
+#define VR_TIMED(...)                                                                             \
+    if (recording) VR_K(v.record = true, __VA_ARGS__);                                            \
+    else if (counting) VR_K(v.count = true, __VA_ARGS__);                                         \
+    VR_TUNING_ARMS(__VA_ARGS__)                                                                   \
+    else if (s16 && one) VR_K(v.stack = STACK_S16, v.s16 = true, v.one = true, __VA_ARGS__);      \
+    else if (s16) VR_K(v.stack = STACK_S16, v.s16 = true, __VA_ARGS__);                           \
+    else if (one) VR_K(v.stack = STACK_ONE, v.one = true, __VA_ARGS__);                           \
+    else VR_K(__VA_ARGS__)
+    const bool whitted = a.scene.integrator == 1;  // WhittedIntegrator: the general-material kernel
     if (c.big) {
         // 64-bit load offsets (scenes past 4 GB of triangles or 2^25 wide nodes): the general
         // kernels only (DARK0 = false and every material kind are always correct, only slower), in
         // the deepest stack class only (launch_render)
-        if constexpr (STACK != 48) return hipErrorInvalidValue;
-        else if (a.scene.integrator == 1) {
-            if (recording) VR_K(STACK, false, true, false, 3, 3, true, false, true);
-            else if (counting) VR_K(STACK, true, false, false, 3, 3, true, false, true);
-            else VR_K(STACK, false, false, false, 3, 3, true, false, true);
+        if constexpr (STACK != 48) {
+            return hipErrorInvalidValue;
+        } else if (whitted) {
+            VR_MODES(v.whitted = true, v.big = true);
         } else {
-            if (recording) VR_K(STACK, false, true, false, 3, 3, false, false, true);
-            else if (counting) VR_K(STACK, true, false, false, 3, 3, false, false, true);
-            else VR_K(STACK, false, false, false, 3, 3, false, false, true);
+            VR_MODES(v.big = true);
         }
         return launch_reduce(a, s, mid);
     }
-    if (a.scene.integrator == 1) {  // WhittedIntegrator: the general-material kernel
-        if (recording) VR_K(STACK, false, true, true, 3, 3, true);
-        else if (counting) VR_K(STACK, true, false, true, 3, 3, true);
-        else VR_K(STACK, false, false, true, 3, 3, true);
+    if (whitted) {
+        VR_MODES(v.dark0 = true, v.whitted = true);
         return launch_reduce(a, s, mid);
     }
     // kinds present (bit 0 Lambertian, 1 reflective, 2 Phong or dielectric) -> specialisation:
     // Lambertian-only (1), reflective-only (2) or the general kernel (3)
     int mats = (c.mats == 1 || c.mats == 2) ? c.mats : 3;
     if (!c.dark0) mats = 3;  // the general kernel
-#ifdef VR_TUNING_VARIANTS  // experiment hooks of tuning builds only (tools/variants.py)
-    // 1..4 = force that many waves per SIMD (default 3); 5 / 6: 16-bit LDS stack entries (trees below
-    // 65,536 wide nodes only) at 4 / 3 waves per SIMD; VR_FORCE_MATS: the material specialisation
-    const char* ve = getenv("VR_KERNEL_VARIANT");
-    const int variant = ve ? atoi(ve) : 0;
+#ifdef VR_TUNING_VARIANTS
     if (const char* fm = getenv("VR_FORCE_MATS")) mats = atoi(fm);
-#define VR_MODES(D, M)                                          \
-    if (recording) VR_K(STACK, false, true, D, M, 3);           \
-    else if (counting) VR_K(STACK, true, false, D, M, 3);       \
-    else if (variant == 1) VR_K(STACK, false, false, D, M, 1);  \
-    else if (variant == 2) VR_K(STACK, false, false, D, M, 2);  \
-    else if (variant == 4) VR_K(STACK, false, false, D, M, 4);  \
-    else if (variant == 5 && STACK == 32) VR_K(STACK, false, false, D, M, 4, false, false, false, false, true); \
-    else if (variant == 6 && STACK == 32) VR_K(STACK, false, false, D, M, 3, false, false, false, false, true); \
-    else if (s16 && one) VR_K(STACK_S16, false, false, D, M, 3, false, false, false, false, true, true); \
-    else if (s16) VR_K(STACK_S16, false, false, D, M, 3, false, false, false, false, true); \
-    else if (one) VR_K(STACK_ONE, false, false, D, M, 3, false, false, false, false, false, true); \
-    else VR_K(STACK, false, false, D, M, 3)
-#else
-#define VR_MODES(D, M)                                                                  \
-    if (recording) VR_K(STACK, false, true, D, M, 3);                                   \
-    else if (counting) VR_K(STACK, true, false, D, M, 3);                               \
-    else if (s16 && one) VR_K(STACK_S16, false, false, D, M, 3, false, false, false, false, true, true); \
-    else if (s16) VR_K(STACK_S16, false, false, D, M, 3, false, false, false, false, true); \
-    else if (one) VR_K(STACK_ONE, false, false, D, M, 3, false, false, false, false, false, true); \
-    else VR_K(STACK, false, false, D, M, 3)
 #endif
     // the cooperative-tail instantiations: launches the host marks (RenderArgs::coop: small launches
     // of scenes with a reflective material)
@@ -2241,16 +2194,18 @@ static hipError_t launch_render_t(const RenderArgs& a, const PoseArgs& pose, con
     constexpr int STACK_ONE = 32;  // (never launched for another class)
     const bool one = c.one_bvh && (s16 || STACK == 32);
     if (!c.dark0) {
-        VR_MODES(false, 3);
+        VR_TIMED(v.dark0 = false);
     } else if (mats == 1) {
-        VR_MODES(true, 1);
+        VR_TIMED(v.dark0 = true, v.mats = 1);
     } else if (mats == 2) {
-        if (coop) VR_K(STACK, false, false, true, 2, VR_COOP_MINW, false, true);
-        else VR_MODES(true, 2);
+        if (coop) VR_K(v.dark0 = true, v.mats = 2, v.minw = VR_COOP_MINW, v.coop = true);
+        else VR_TIMED(v.dark0 = true, v.mats = 2);
     } else {
-        if (coop) VR_K(STACK, false, false, true, 3, VR_COOP_MINW, false, true);
-        else VR_MODES(true, 3);
+        if (coop) VR_K(v.dark0 = true, v.mats = 3, v.minw = VR_COOP_MINW, v.coop = true);
+        else VR_TIMED(v.dark0 = true, v.mats = 3);
     }
+#undef VR_TIMED
+#undef VR_TUNING_ARMS
 #undef VR_MODES
 #undef VR_K
     return launch_reduce(a, s, mid);
@@ -2313,32 +2268,6 @@ int launch_trace(const TraceArgs& a, int stack_depth, void* stream) {
     else return -1000;
     return (int)hipGetLastError();
 }
-
-#ifdef VR_SPLIT_PROBE
-// analysis builds: the traversal-only instantiations (TRACE) of the render kernel over a ray buffer,
-// at `minw` waves per SIMD, with 32- or 16-bit LDS stack entries
-int launch_trace_probe(const RenderArgs& a, int stack_depth, int minw, bool s16, int grid, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    dim3 g((unsigned)grid), b(256);
-#define VR_KT(ST, MW, S16_)                                                                                    \
-    hipLaunchKernelGGL((dev::render_kernel<ST, false, false, true, 3, MW, false, false, false, true, S16_>), g, b, \
-                       0, s, a, a.scene.prims, a.scene.materials, a.scene.bvhs, PoseArgs{}, LensArgs{})
-    if (stack_depth > 32) return -1000;
-    if (s16) {
-        if (minw == 3) VR_KT(32, 3, true);
-        else if (minw == 4) VR_KT(32, 4, true);
-        else if (minw == 5) VR_KT(32, 5, true);
-        else if (minw == 6) VR_KT(32, 6, true);
-        else return -1001;
-    } else {
-        if (minw == 3) VR_KT(32, 3, false);
-        else if (minw == 4) VR_KT(32, 4, false);
-        else return -1001;
-    }
-#undef VR_KT
-    return (int)hipGetLastError();
-}
-#endif
 
 const char* device_error_string(int code) {
     if (code == -1000) return "BVH deeper than the largest traversal stack (48)";
