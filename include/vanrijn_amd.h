@@ -897,7 +897,16 @@ int vr_scene_needs_wide_offsets(uint64_t triangle_count, uint64_t wide_node_coun
 #define VR_CHOICE_COOP_GATED 8u   /* small enough for the cooperative tail, with or without VR_LAUNCH_NO_COOP */
 #define VR_CHOICE_WIDE_OFFSETS 16u /* the 64-bit-offset kernels */
 #define VR_CHOICE_MULTI_BVH 32u   /* VR_LAUNCH_MULTI_BVH */
+#define VR_CHOICE_OWN_GRIDS 64u   /* one material kind, and the rows' wavelength grids differ (vr_scene_grid_shared bit 0 clear) */
 int vr_launch_takes_one_bvh(uint64_t bvh_count, int32_t root4, uint32_t other, int32_t stack_depth, int32_t stack16);
+/* 1 when the `count` material rows at `rows` (vr_scene_materials' records) lie on one wavelength grid:
+ * shortest, longest, n, inv_step and knots[0..n) equal bit for bit.  vr_scene_grid_shared: the same of
+ * the rows of `scene`, kept up to date by the edits: bit 0, its materials and Whitted light rows share a
+ * grid; bit 1 (never without bit 0), the sky row lies on it too.  The single-BVH kernels of one material
+ * kind, which look a path's wavelength up once, need bit 0 and use bit 1.  Host only (additions under
+ * ABI 10). */
+int vr_material_grids_shared(const void* rows, uint32_t count);
+int vr_scene_grid_shared(const vr_scene* scene);
 /* The VR_VARIANT_* bits a render of `pixel_samples` (tile pixels x spp) of `scene` with `launch_flags`
  * would report now (recording: the per-sample record variant).  Launches nothing; host-only scenes too. */
 int vr_scene_launch_variant(const vr_scene* scene, uint64_t pixel_samples, uint32_t launch_flags, int32_t recording,

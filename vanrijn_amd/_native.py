@@ -30,6 +30,7 @@ LAUNCH_NO_DIST_CULL, LAUNCH_NO_COOP, LAUNCH_NO_LONE_WALK, LAUNCH_STACK32, LAUNCH
 VARIANT_COOP, VARIANT_WIDE_OFFSETS, VARIANT_STACK16, VARIANT_ONE_BVH = 1, 2, 4, 8
 # vr_launch_takes_one_bvh's `other`: what else a launch selected
 CHOICE_COUNTING, CHOICE_RECORD, CHOICE_WHITTED, CHOICE_COOP_GATED, CHOICE_WIDE_OFFSETS, CHOICE_MULTI_BVH = 1, 2, 4, 8, 16, 32
+CHOICE_OWN_GRIDS = 64
 SCENE_INFO_NAN_FREE = 1
 
 
@@ -248,6 +249,8 @@ SIGNATURES = {
     "vr_debug_set_launch_flags": (C.c_int, [_p, _u32]),
     "vr_scene_needs_wide_offsets": (C.c_int, [_u64, _u64]),
     "vr_launch_takes_one_bvh": (C.c_int, [_u64, C.c_int32, _u32, C.c_int32, C.c_int32]),
+    "vr_material_grids_shared": (C.c_int, [_p, _u32]),
+    "vr_scene_grid_shared": (C.c_int, [_p]),
     "vr_scene_launch_variant": (C.c_int, [_p, _u64, _u32, C.c_int32, C.POINTER(_u32)]),
     "vr_device_count": (C.c_int, []),
     "vr_last_error": (C.c_char_p, []),

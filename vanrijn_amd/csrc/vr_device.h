@@ -173,6 +173,39 @@ __device__ __forceinline__ double material_intensity(const Material* m, double w
     return spectrum_fast(m, wl, [&](int j) { return m->samples[j]; });
 }
 
+// spectrum_fast in two steps, for scenes whose intensity rows all lie on one wavelength grid (the
+// host's proof, vr_host_scene.cpp update_grid_shared; `g` is the scene's one copy of it, a wave-uniform
+// row): what depends on the wavelength and the grid alone is found once per path (path_segment, where
+// the wavelength is drawn), and each lookup of the path blends its row's two samples with it
+// (spectrum_path).  The expressions are spectrum_fast's on the same operands in the same order, so the
+// values are its values bit for bit.  seg: -1 out of range (intensity 0), n - 1 the last knot (its
+// sample as it is), else the segment.
+__device__ __forceinline__ void path_segment(const Material* g, double wl, int& seg, double& ratio) {
+    seg = -1;
+    ratio = 0.0;
+    if (wl < g->shortest || wl > g->longest) return;
+    const int n = g->n;
+    int i = (int)((wl - g->shortest) * g->inv_step);
+    i = i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
+    seg = i;
+    if (i == n - 1) return;
+    const double before = g->knots[i], after = g->knots[i + 1];
+    ratio = (wl - before) / (after - before);
+}
+template <class F>
+__device__ __forceinline__ double spectrum_path(const Material* g, int seg, double ratio, F sample) {
+    if (seg < 0) return 0.0;
+    if (seg == g->n - 1) return sample(seg);
+    return sample(seg) * (1.0 - ratio) + sample(seg + 1) * ratio;
+}
+// spectrum_fast of `m`'s samples on the shared grid's copy `g` (scalar reads where `m` is a lane's own row)
+__device__ __forceinline__ double material_intensity_on(const Material* m, const Material* g, double wl) {
+    return spectrum_fast(g, wl, [&](int j) { return m->samples[j]; });
+}
+__device__ __forceinline__ double material_intensity_path(const Material* m, const Material* g, int seg, double ratio) {
+    return spectrum_path(g, seg, ratio, [&](int j) { return m->samples[j]; });
+}
+
 // ----------------------------------------------------------------------------------------------
 // Phong and dielectric materials (materials/phong_material.rs, smooth_transparent_dialectric.rs)
 // ----------------------------------------------------------------------------------------------
@@ -250,7 +283,9 @@ __device__ __forceinline__ double dielectric_strength(const Fresnel& f, V3 w_o) 
 
 // test_lighting_environment (simple_random_integrator.rs:57-65): reflection_from_linear_rgb of
 // (w.y, w.y, 1) (spectrum.rs:81-165), evaluated only at the two samples the lookup needs.
-__device__ double sky_intensity(double wy, double wl, const Material* knots) {
+// `lookup` evaluates a spectrum given by its samples (spectrum_fast, or a path's spectrum_path).
+template <class L>
+__device__ __forceinline__ double sky_spectrum(double wy, L lookup) {
     const double r = wy, g = wy, b = 1.0;
     double c0, c1, c2;
     int kx, ky;
@@ -264,9 +299,16 @@ __device__ double sky_intensity(double wy, double wl, const Material* knots) {
         if (r <= g) { c0 = b; c1 = r - b; c2 = g - r; kx = VR_RGBSPEC_YELLOW; ky = VR_RGBSPEC_GREEN; }
         else { c0 = b; c1 = g - b; c2 = r - g; kx = VR_RGBSPEC_YELLOW; ky = VR_RGBSPEC_RED; }
     }
-    return spectrum_fast(knots, wl, [&](int j) {
+    return lookup([&](int j) {
         return c0 * c_rgbspec[VR_RGBSPEC_WHITE][j] + c1 * c_rgbspec[kx][j] + c2 * c_rgbspec[ky][j];
     });
+}
+__device__ double sky_intensity(double wy, double wl, const Material* knots) {
+    return sky_spectrum(wy, [&](auto sample) { return spectrum_fast(knots, wl, sample); });
+}
+// the same with the path's segment and ratio on the shared grid `g` (path_segment)
+__device__ double sky_intensity_path(double wy, const Material* g, int seg, double ratio) {
+    return sky_spectrum(wy, [&](auto sample) { return spectrum_path(g, seg, ratio, sample); });
 }
 
 __device__ __forceinline__ double gaussian(double wl, double alpha, double mu, double s1, double s2) {

@@ -28,7 +28,8 @@ static bool needs_big_offsets(uint64_t tri_count, uint64_t wide_count) {
 // root (render_kernel<.., ONE>: no list walk, no per-lane BVH cursor; round 8).  `root4`: that BVH's
 // root (negative: a one-triangle mesh, or INT32_MIN for an empty one).  `other`: VR_CHOICE_* bits of
 // what else the launch selected -- the counting, record, Whitted and 64-bit-offset kernels have no such
-// instantiation, VR_LAUNCH_MULTI_BVH asks for the generic kernel, and a launch small enough for the
+// instantiation, VR_LAUNCH_MULTI_BVH asks for the generic kernel, a scene of one material kind whose
+// rows lie on different wavelength grids runs it too (VR_CHOICE_OWN_GRIDS), and a launch small enough for the
 // cooperative tail keeps the kernels it had, with the tail or (VR_LAUNCH_NO_COOP) without it, so that
 // flag's A/B still isolates the tail.  It exists with 16-bit stack entries in the 24 and 32 stack classes
 // and with 32-bit ones in the 32 class (vr_render.hip launch_render_t).
@@ -66,7 +67,10 @@ static vr::LaunchChoice launch_choice(const vr_scene* s, bool coop, bool gated, 
     const uint32_t other = (counting ? VR_CHOICE_COUNTING : 0u) | (recording ? VR_CHOICE_RECORD : 0u) |
                            (s->dev.integrator == 1 ? VR_CHOICE_WHITTED : 0u) | (gated || lc.coop ? VR_CHOICE_COOP_GATED : 0u) |
                            (lc.big ? VR_CHOICE_WIDE_OFFSETS : 0u) |
-                           ((launch_flags & VR_LAUNCH_MULTI_BVH) ? VR_CHOICE_MULTI_BVH : 0u);
+                           ((launch_flags & VR_LAUNCH_MULTI_BVH) ? VR_CHOICE_MULTI_BVH : 0u) |
+                           // the single-BVH kernels of one material kind look a path's wavelength up once,
+                           // on the one grid every row shares (vr_render.hip PATHWL)
+                           (lc.dark0 && (lc.mats == 1 || lc.mats == 2) && !s->grid_shared ? VR_CHOICE_OWN_GRIDS : 0u);
     lc.one_bvh = takes_one_bvh(s->bvhs.size(), s->bvhs.empty() ? INT32_MIN : s->bvhs[0].root4, other, stack, lc.s16);
     return lc;
 }
@@ -221,6 +225,7 @@ vr::RenderArgs make_args(const vr_scene* s, const vr_render_params* p, double* s
     a.accumulate = p->accumulate;
     a.state = state;  // (queue, staging, error word, cull mask, records, counters: per call, enqueue_passes)
     a.fault_object = s->fault_object;
+    a.sky_on_grid = s->sky_on_grid ? 1u : 0u;
     const char* th = tuning_env("VR_SHADE_THRESHOLD");  // tuning hook (tools/variants.py)
     a.shade_threshold = th ? (uint32_t)atoi(th) : 52u;
     const char* sm = tuning_env("VR_SHADE_MIN");  // tuning hook: defer shading below this many hits
@@ -565,6 +570,12 @@ static int sum_pass_times(const std::vector<hipEvent_t>& ev, T* kernel_ms, T* re
 int vr_scene_needs_wide_offsets(uint64_t triangle_count, uint64_t wide_node_count) {
     return needs_big_offsets(triangle_count, wide_node_count) ? 1 : 0;
 }
+
+int vr_material_grids_shared(const void* rows, uint32_t count) {
+    return rows && grids_shared((const vr::Material*)rows, count) ? 1 : 0;
+}
+
+int vr_scene_grid_shared(const vr_scene* s) { return s ? (s->grid_shared ? 1 : 0) | (s->sky_on_grid ? 2 : 0) : 0; }
 
 int vr_launch_takes_one_bvh(uint64_t bvh_count, int32_t root4, uint32_t other, int32_t stack_depth, int32_t stack16) {
     return takes_one_bvh(bvh_count, root4, other, stack_depth, stack16 != 0) ? 1 : 0;

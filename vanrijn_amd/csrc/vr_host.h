@@ -166,6 +166,10 @@ struct vr_scene {
     std::vector<double> mesh_extent;      // max |coordinate| of each mesh
     std::vector<uint8_t> mesh_finite;     // shading_finite of each mesh (1 where no object traces it)
     bool dark0_materials = true;          // dark0's materials-only part
+    // the rows of `materials` lie on one wavelength grid, bit for bit (update_grid_shared): the desc's
+    // materials and the Whitted light rows (grid_shared), and the sky row as well (sky_on_grid, never set
+    // without grid_shared); materials[0] is the scene's copy of that grid
+    bool grid_shared = false, sky_on_grid = false;
     std::vector<int> mesh_object;         // the BVH object a mesh backs, or -1
     std::vector<int> mesh_bvh;            // its record in bvhs, or -1
     std::vector<uint32_t> mesh_material;  // vr_mesh_desc::material (what TriNormals::material1 == 0 stands for)
@@ -259,6 +263,8 @@ const char* prim_row(const vr_primitive_desc& p, int32_t object, int32_t positio
 void update_base_extent(vr_scene* s);
 void update_material_scalars(vr_scene* s);
 void update_scalars(vr_scene* s);
+bool grids_shared(const vr::Material* rows, size_t count);
+void update_grid_shared(vr_scene* s);
 
 // vr_host.cpp: the call-context pool and the render path
 void ctx_free_all(CallCtx* c);

@@ -459,6 +459,7 @@ int vr_scene_update_material(vr_scene* s, uint32_t index, const vr_material_desc
     if (const char* why = material_row(*material, row)) return fail(VR_ERROR_INVALID_ARGUMENT, why);
     s->materials[index] = row;
     update_material_scalars(s);
+    update_grid_shared(s);
     update_scalars(s);
     return copy_rows(s, s->dev.materials, sizeof(vr::Material), index, &s->materials[index], 1);
 }
@@ -473,6 +474,7 @@ int vr_scene_set_lights(vr_scene* s, const vr_integrator_desc* integrator) {
     std::vector<double> dirs;
     if (const char* why = light_rows(*integrator, rows, dirs)) return fail(VR_ERROR_INVALID_ARGUMENT, why);
     std::copy(rows.begin(), rows.end(), s->materials.begin() + s->dev.light_base);
+    update_grid_shared(s);
     s->light_dirs = dirs;
     const int rc = copy_rows(s, s->dev.materials, sizeof(vr::Material), (size_t)s->dev.light_base, rows.data(), rows.size());
     return rc ? rc : copy_rows(s, s->dev.light_dirs, sizeof(double), 0, dirs.data(), dirs.size());

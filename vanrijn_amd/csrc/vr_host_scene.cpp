@@ -177,6 +177,30 @@ void update_material_scalars(vr_scene* s) {
     }
 }
 
+// The wavelength grid of a row is what the device's intensity lookup reads beside the samples:
+// shortest, longest, n, inv_step and knots[0..n).  True when every row's equals the first row's bit
+// for bit (compared as bytes: -0.0 is not 0.0, a NaN equals only itself).
+bool grids_shared(const vr::Material* rows, size_t count) {
+    for (size_t i = 1; i < count; ++i) {
+        const vr::Material &a = rows[0], &b = rows[i];
+        if (a.n != b.n || a.n < 0 || a.n > vr::kMaxSpectrumSamples) return false;
+        if (std::memcmp(&a.shortest, &b.shortest, sizeof(double)) || std::memcmp(&a.longest, &b.longest, sizeof(double)) ||
+            std::memcmp(&a.inv_step, &b.inv_step, sizeof(double)) ||
+            std::memcmp(a.knots, b.knots, sizeof(double) * (size_t)a.n))
+            return false;
+    }
+    return true;
+}
+
+// At creation and after every edit that writes a material or light row (nothing writes the sky row, the
+// last one).  The render kernels that find a path's segment and ratio once, on row 0's grid, run only
+// while the material and light rows share it (vr_host.cpp launch_choice); a sky row on another grid --
+// a scene of two-sample grey materials, say -- keeps its own lookup there (RenderArgs::sky_on_grid).
+void update_grid_shared(vr_scene* s) {
+    s->grid_shared = grids_shared(s->materials.data(), (size_t)s->dev.sky_row);
+    s->sky_on_grid = s->grid_shared && grids_shared(s->materials.data(), s->materials.size());
+}
+
 void update_scalars(vr_scene* s) {
     double extent = s->base_extent;
     for (double e : s->mesh_extent) extent = std::max(extent, e);
@@ -388,6 +412,7 @@ int vr_scene_create(const vr_scene_desc* desc, int32_t device, uint32_t flags, v
         s->dev.sky_row = (int32_t)s->materials.size();
         s->materials.push_back(sky);
     }
+    update_grid_shared(s);
     // objects: primitive lists keep their order; BVHs are built per mesh
     std::vector<int> mesh_object(desc->mesh_count, -1);
     s->prim_rows.resize(desc->primitive_count);

@@ -224,7 +224,11 @@ struct RenderArgs {
     // nullptr: every block of the tile is live
     const uint32_t* live_blocks;
     const uint32_t* live_count;
-    uint64_t reserved[4];  // unused: keeps the kernel-argument offsets of the members below (moving them moves spills)
+    // 1: the sky row lies on the wavelength grid the material rows share (materials[0]'s; vr_host_scene.cpp
+    // update_grid_shared), so a path's segment and ratio serve the sky lookup too (vr_render.hip PATHWL)
+    uint32_t sky_on_grid;
+    uint32_t reserved32;
+    uint64_t reserved[3];  // unused: keeps the kernel-argument offsets of the members below (moving them moves spills)
     // debug builds only (-DVR_STAGE_GUARD, DESIGN.md section 8 "staging invariant"): beside every
     // staged photon the launch's generation, which the ordered reduce checks before reading it
     uint32_t* stage_tag;  // [pass sample][tile pixel], or nullptr

@@ -361,6 +361,24 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
     int depth = -1, bounces = 0, flags = 0;
     double lambda = 0.0, T = 1.0, Acc = 0.0, T0 = 1.0, Acc0 = 0.0, b0 = 0.0, wo_y = 0.0;
     double Wa = 0.0, Wb = 0.0;  // Whitted: the pending continuation's throughput and constant
+    // PATHWL: the ONE kernels of one material kind look intensities up on the one wavelength grid the scene's
+    // material rows share (the host launches them for no other scene: vr_host.cpp launch_choice), read from
+    // its wave-uniform copy, row 0, with scalar loads; every other instantiation keeps spectrum_fast on
+    // the lane's own row, and its code.
+    // CARRY: of these the Lambertian-only ones find the wavelength's segment and ratio on that grid once
+    // per path, where lambda is drawn (vr_device.h path_segment), and every intensity lookup of the path --
+    // the surface colour in shade, the sky at its end -- blends its two samples with them instead of finding
+    // them again (two range compares, the index, two dependent knot loads and an f64 division per lookup).
+    // The three registers come from the `flags` word, which these kernels do not have (NOFLAGS): no
+    // Lambertian surface cuts a path (kPathCut is a mirror's or a Phong surface's), and bits 1, 2 and 4 are
+    // the record kernels'.  The reflective-only ones need the word and spill already: carrying the ratio,
+    // alone or with the segment, cost them 8 to 32 B more scratch, so they keep the lookup whole.
+    constexpr bool PATHWL = ONE && DARK0 && (MATS == 1 || MATS == 2) && !WHITTED && !COUNT && !RECORD;
+    constexpr bool CARRY = PATHWL && MATS == 1, NOFLAGS = CARRY;
+#define VR_PATH_CUT (!NOFLAGS && (flags & kPathCut))
+    const Material* const grid = S.materials;
+    int wl_seg = -1;
+    double wl_ratio = 0.0;
 
     // BVH cull: subtree entirely beyond the closest hit (+margin) or behind the origin
     auto culled = [&](double tlo, double thi) {
@@ -801,7 +819,9 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
             state = kRayReady;
             return;
         }
-        const double c_l = material_intensity(mat, lambda);
+        const double c_l = CARRY    ? material_intensity_path(mat, grid, wl_seg, wl_ratio)
+                           : PATHWL ? material_intensity_on(mat, grid, lambda)
+                                    : material_intensity(mat, lambda);
         const double c_0 = DARK0 ? 0.0 : material_intensity(mat, 0.0);
         double a, a0, bterm;
         bool cut = false;  // this level's bsdf returns the constant 0 whatever comes from below
@@ -845,7 +865,7 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
         // trapped path of a scene scaled by 1e20 does) is discarded, where T * a would turn the
         // forward product 0 * NaN.  From the cut on (kPathCut in `flags`, cleared per path and masked
         // out of the record) the products are frozen and the path's end adds nothing.
-        if (!(flags & kPathCut)) {
+        if (!VR_PATH_CUT) {
             Acc = Acc + T * bterm;
             T = T * a;
             if (!DARK0) {
@@ -853,7 +873,7 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                 T0 = T0 * a0;
             }
         }
-        if (cut) flags |= kPathCut;
+        if (!NOFLAGS && cut) flags |= kPathCut;
         // A path whose every continuation yields intensity 0 stops here -- only in scenes the host
         // proved NaN-free (A.early_stop: every mesh triangle's shading basis is finite for any
         // barycentric point, no Phong / dielectric): the reference keeps recursing and returns
@@ -1259,23 +1279,27 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
                     if (!best.kind) {
                         finish(0.0, 0.0);  // camera ray missed: photon {0, 0} (camera.rs:110-113)
                     } else {
-                        flags |= 1;
+                        if (!NOFLAGS) flags |= 1;
                         lambda = 380.0 + (740.0 - 380.0) * rng.standard();  // Photon::random_wavelength
+                        if constexpr (CARRY) path_segment(grid, lambda, wl_seg, wl_ratio);
                         T = 1.0; Acc = 0.0; T0 = 1.0; Acc0 = 0.0; b0 = 0.0;
                         depth = 0;
                         go = true;
                     }
                 } else if (!best.kind) {
                     // simple_random_integrator.rs:43-46; below a cut level the sky term is discarded too
-                    finish(lambda, (flags & kPathCut) ? Acc : Acc + T * sky_intensity(wo_y, lambda, &S.materials[S.sky_row]));
+                    // (CARRY: a sky row on another grid than the materials' keeps its own lookup)
+                    finish(lambda, VR_PATH_CUT              ? Acc
+                                   : CARRY && A.sky_on_grid ? Acc + T * sky_intensity_path(wo_y, grid, wl_seg, wl_ratio)
+                                                            : Acc + T * sky_intensity(wo_y, lambda, &S.materials[S.sky_row]));
                 } else {
                     depth += 1;
                     if (depth == kRecursionLimit) {  // integrate(.., 0) returns {0, 0}: lambda becomes 0
-                        flags |= 2;
+                        if (!NOFLAGS) flags |= 2;
                         // the innermost photon's intensity 0 times the lambda-0 throughput: + 0
                         // when finite, NaN when a level's pdf * |cos| was (the reference's 0 * NaN);
                         // DARK0 scenes are NaN-free (host), where every lambda-0 level is 0 * I + b
-                        finish(0.0, DARK0 ? b0 : (flags & kPathCut) ? Acc0 : Acc0 + T0 * 0.0);
+                        finish(0.0, DARK0 ? b0 : VR_PATH_CUT ? Acc0 : Acc0 + T0 * 0.0);
                     } else {
                         go = true;
                     }

@@ -530,6 +530,17 @@ class DeviceScene:
                                                 C.byref(v)))
         return v.value
 
+    def grid_shared(self):
+        """vr_scene_grid_shared: bit 0, the material and Whitted light rows lie on one wavelength grid bit
+        for bit; bit 1 (never without bit 0), the sky row lies on it too."""
+        return int(N.lib().vr_scene_grid_shared(self.handle))
+
+    @classmethod
+    def grids_shared(cls, rows):
+        """vr_material_grids_shared of material rows (materials()' structured array)."""
+        rows = np.ascontiguousarray(rows, dtype=cls.MATERIAL_DTYPE)
+        return bool(N.lib().vr_material_grids_shared(rows.ctypes.data_as(C.c_void_p), len(rows)))
+
     def set_fault_object(self, obj):
         """Test hook (vr_debug_set_fault_object): hits on scene object `obj` report the singular
         shading basis (VR_ERROR_SINGULAR_BASIS); -1 turns it off."""
