@@ -10,7 +10,8 @@ LIB = os.path.join(LIB_DIR, "libvanrijn_amd.so")
 SOURCES = ["vr_render.hip", "vr_query.hip", "vr_integrate.hip", "vr_image.hip", "vr_build.hip", "vr_refit.hip",
            "vr_host.cpp", "vr_host_bvh.cpp", "vr_host_scene.cpp", "vr_host_edit.cpp", "vr_host_rays.cpp",
            "vr_host_film.cpp", "vr_host_io.cpp"]
-HEADERS = ["vr_host.h", "vr_layout.h", "vr_device.h", "vr_walk4.h", "vr_refit.h", "vr_camera.h", "rgb_spectrum_tables.h", "vr_exp_table.h",
+HEADERS = ["vr_host.h", "vr_layout.h", "vr_device.h", "vr_shade.h", "vr_walk4.h", "vr_refit.h", "vr_camera.h", "rgb_spectrum_tables.h",
+           "vr_exp_table.h",
            os.path.join("..", "..", "include", "vanrijn_amd.h")]
 
 FLAGS = [

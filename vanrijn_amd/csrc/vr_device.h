@@ -973,39 +973,6 @@ __device__ bool any_hit(const DeviceScene& S, const RayPre& p, uint32_t* st, int
     return false;
 }
 
-// Material::bsdf as an affine map of the incoming intensity: out = a * I + b, for the
-// WhittedIntegrator's calls (bsdf(w_o, w_i, photon)); lambertian_material.rs:27-34,
-// reflective_material.rs:15-40, phong_material.rs:17-36, smooth_transparent_dialectric.rs:79-95
-__device__ __forceinline__ void bsdf_affine(const Material* m, V3 w_o, V3 w_i, double wl, double& a, double& b) {
-    b = 0.0;
-    if (m->kind == 1) {
-        if (w_i.z <= 0.0 || w_o.z <= 0.0) {
-            a = 0.0;
-            return;
-        }
-        const V3 refl = mk(-w_o.x, -w_o.y, w_o.z);
-        double c = dot(w_i, refl);
-        c = c < 0.0 ? 0.0 : (c > 1.0 ? 1.0 : c);
-        const double theta = acos(fabs(c));
-        const double sigma = 0.05, two = 2.0;
-        const double f = m->reflection * exp(-(pow(theta, two)) / (two * sigma * sigma));
-        a = (material_intensity(m, wl) * m->diffuse) * (1.0 - f);
-        b = f;
-    } else if (m->kind == 2) {
-        if (w_i.z < 0.0 || w_o.z < 0.0) {
-            a = 0.0;
-            return;
-        }
-        const V3 refl = mk(-w_i.x, -w_i.y, w_i.z);
-        a = material_intensity(m, wl) * m->diffuse;
-        b = pow(fabs(dot(w_o, refl)), m->smoothness) * (m->reflection / dot(w_i, mk(0.0, 0.0, 1.0)));
-    } else if (m->kind == 3) {
-        a = dielectric_strength(dielectric_fresnel(m, w_i, wl), w_o);
-    } else {
-        a = material_intensity(m, wl) * m->diffuse;
-    }
-}
-
 // ONE: the scene's only BVH owns every triangle hit (render_kernel's ONE instantiations)
 template <bool ONE = false>
 __device__ __forceinline__ void hit_info(const DeviceScene& S, const Best& best, const RayPre& p, HitInfo& h) {

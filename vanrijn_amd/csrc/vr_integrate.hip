@@ -9,10 +9,11 @@
 // out of rays.
 //
 // Traversal is vr_walk4.h's per-lane walk of the 4-wide tree (closest hit for path rays, any hit for
-// the Whitted shadow rays, on the same LDS stack).  Shading is render_kernel's `shade` lambda and the
-// transitions around it (vr_render.hip) restated for one lane, the same operations in the same order
-// with the general lambda-0 pair (T0, Acc0) and every material kind compiled in: under
-// -ffp-contract=off the photons equal the megakernel's bit for bit.
+// the Whitted shadow rays, on the same LDS stack).  One shading level is vr_shade.h's, the functions
+// render_kernel's `shade` lambda calls too (vr_render.hip), with the general lambda-0 pair (T0, Acc0)
+// and every material kind compiled in; the path state and the transitions around a level are that
+// kernel's restated for one lane, the same operations in the same order: under -ffp-contract=off the
+// photons equal the megakernel's bit for bit.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -23,6 +24,7 @@
 #include "vr_camera.h"
 
 #include "vr_device.h"
+#include "vr_shade.h"
 #include "vr_walk4.h"
 
 namespace vr {
@@ -109,11 +111,7 @@ __global__ __launch_bounds__(256) void integrate_kernel(IntegrateArgs A) {
         if (go) do {
             HitInfo h;
             hit_info(S, best, pre, h);
-            // world_to_bsdf = rows(tangent, cotangent, normal) (algebra_utils.rs:3-5); its
-            // determinant via the first-row minors (mat3.rs:106-109)
-            const double det = h.tangent.x * (h.cotangent.y * h.normal.z - h.cotangent.z * h.normal.y) -
-                               h.tangent.y * (h.cotangent.x * h.normal.z - h.cotangent.z * h.normal.x) +
-                               h.tangent.z * (h.cotangent.x * h.normal.y - h.cotangent.y * h.normal.x);
+            const double det = basis_det(h);
             // try_inverse() == None: the reference panics; the fault_object test hook takes this path
             if (det == 0.0 || best.object == A.fault_object) {
                 flags |= 4;
@@ -124,27 +122,10 @@ __global__ __launch_bounds__(256) void integrate_kernel(IntegrateArgs A) {
             const V3 w_i = mk(dot(h.tangent, h.retro), dot(h.cotangent, h.retro), dot(h.normal, h.retro));
             const Material* mat = &S.materials[h.material];
             if constexpr (WHITTED) {
-                // light terms, in order (fold from the camera photon's intensity 0): a shadow ray per
-                // light; blocked -> the ambient spectrum, else bsdf(W retro, W dir, light(lambda) |dir.n|)
-                double C = 0.0;
-                for (int j = 0; j < S.light_count; ++j) {
-                    const V3 ldir = ldv(S.light_dirs + 3 * j);
-                    const V3 d1 = normalize(ldir);
-                    const RayPre sp = prepare(Ray{add(h.loc, scl(d1, kBounceBias)), normalize_n1(d1)});
-                    double term;
+                Acc = Acc + T * whitted_direct(S, h, mat, w_i, lambda, [&](const RayPre& sp) {
                     Best unused;
-                    if (walk4<STACK, true>(S, sp, st, tid, unused)) {
-                        term = material_intensity(&S.materials[S.light_base], lambda);
-                    } else {
-                        const V3 wl = mk(dot(h.tangent, ldir), dot(h.cotangent, ldir), dot(h.normal, ldir));
-                        const double I = material_intensity(&S.materials[S.light_base + 1 + j], lambda) * fabs(dot(ldir, h.normal));
-                        double ba, bb;
-                        bsdf_affine(mat, w_i, wl, lambda, ba, bb);
-                        term = ba * I + bb;
-                    }
-                    C = C + term;
-                }
-                Acc = Acc + T * C;
+                    return walk4<STACK, true>(S, sp, st, tid, unused);
+                });
                 if (depth >= kRecursionLimit) {  // recursion_limit 0: the continuation contributes 0
                     flags |= 2;
                     finish(lambda, Acc);
@@ -155,48 +136,9 @@ __global__ __launch_bounds__(256) void integrate_kernel(IntegrateArgs A) {
             double pdf;
             const int kind = mat->kind;
             Fresnel fr;  // dielectric only
-            if (kind == 1) {  // reflective_material.rs:42-47
-                w_o = mk(-w_i.x, -w_i.y, w_i.z);
-                pdf = 1.0;
-            } else if (kind == 2) {  // Phong: Material::sample's default (materials/mod.rs:28-33)
-                w_o = cosine_weighted_hemisphere(rng);
-                pdf = cosine_weighted_pdf(w_o);
-            } else if (kind == 3) {  // smooth_transparent_dialectric.rs:97-114
-                fr = dielectric_fresnel(mat, w_i, lambda);
-                pdf = 0.5;
-                if (fr.T <= 0.0000000001) w_o = fr.rdir;
-                else if (fr.R <= 0.0000000001 || rng.boolean()) w_o = fr.tdir;
-                else w_o = fr.rdir;
-            } else {  // lambertian_material.rs:36-59: rejection sampling on Open01 pairs
-                double x = 2.0 * rng.open01() - 1.0;
-                double y = 2.0 * rng.open01() - 1.0;
-                while (dot(mk(x, y, 0.0), mk(x, y, 0.0)) > 1.0) {
-                    x = 2.0 * rng.open01() - 1.0;
-                    y = 2.0 * rng.open01() - 1.0;
-                }
-                const double z = fmax(sqrt(1.0 - x * x - y * y), 0.0);
-                const V3 w = mk(x, y, z);
-                const double cos_theta = dot(w, mk(0.0, 0.0, 1.0));
-                const double sin_theta = sqrt(1.0 - cos_theta * cos_theta);
-                w_o = normalize_n1(w);  // |w|^2 = x^2 + y^2 + (1 - x^2 - y^2): 1 within a few spacings
-                pdf = (cos_theta * sin_theta) / 3.14159265358979323846;
-            }
-            // bsdf_to_world = cofactor(M)^T * det (mat3.rs:111-118), applied to w_o by rows
-            V3 wo_world;
-            {
-                const double m00 = h.tangent.x, m01 = h.tangent.y, m02 = h.tangent.z;
-                const double m10 = h.cotangent.x, m11 = h.cotangent.y, m12 = h.cotangent.z;
-                const double m20 = h.normal.x, m21 = h.normal.y, m22 = h.normal.z;
-                const V3 inv0 = mk((1.0 * (m11 * m22 - m12 * m21)) * det, (-1.0 * (m01 * m22 - m02 * m21)) * det,
-                                   (1.0 * (m01 * m12 - m02 * m11)) * det);
-                wo_world.x = dot(inv0, w_o);
-                const V3 inv1 = mk((-1.0 * (m10 * m22 - m12 * m20)) * det, (1.0 * (m00 * m22 - m02 * m20)) * det,
-                                   (-1.0 * (m00 * m12 - m02 * m10)) * det);
-                wo_world.y = dot(inv1, w_o);
-                const V3 inv2 = mk((1.0 * (m10 * m21 - m11 * m20)) * det, (-1.0 * (m00 * m21 - m01 * m20)) * det,
-                                   (1.0 * (m00 * m11 - m01 * m10)) * det);
-                wo_world.z = dot(inv2, w_o);
-            }
+            if (kind == 3) fr = sample_dielectric(mat, w_i, lambda, rng, w_o, pdf);
+            else sample_bsdf<3>(kind, w_i, rng, w_o, pdf);
+            const V3 wo_world = bsdf_to_world(h, det, w_o);
             const double cosf = fabs(dot(wo_world, h.normal));
             if constexpr (WHITTED) {
                 // continuation: bsdf(W retro, dir, L_next) |dir.n|, applied when its ray hits
@@ -209,38 +151,8 @@ __global__ __launch_bounds__(256) void integrate_kernel(IntegrateArgs A) {
                 const double c_0 = material_intensity(mat, 0.0);
                 double a, a0, bterm;
                 bool cut = false;  // this level's bsdf returns the constant 0 whatever comes from below
-                if (kind == 1) {  // reflective_material.rs:17-39
-                    if (w_i.z <= 0.0 || w_o.z <= 0.0) {
-                        a = 0.0; a0 = 0.0; bterm = 0.0; cut = true;
-                    } else {
-                        const V3 refl = mk(-w_o.x, -w_o.y, w_o.z);
-                        double cth = dot(w_i, refl);
-                        cth = cth < 0.0 ? 0.0 : (cth > 1.0 ? 1.0 : cth);
-                        const double theta = acos(fabs(cth));
-                        const double sigma = 0.05, two = 2.0;
-                        const double f = mat->reflection * exp(-(pow(theta, two)) / (two * sigma * sigma));
-                        a = (((pdf * cosf) * c_l) * mat->diffuse) * (1.0 - f);
-                        a0 = (((pdf * cosf) * c_0) * mat->diffuse) * (1.0 - f);
-                        bterm = f;
-                    }
-                } else if (kind == 2) {  // phong_material.rs:17-36: diffuse + specular lobe
-                    if (w_i.z < 0.0 || w_o.z < 0.0) {
-                        a = 0.0; a0 = 0.0; bterm = 0.0; cut = true;
-                    } else {
-                        const V3 refl = mk(-w_i.x, -w_i.y, w_i.z);
-                        a = ((pdf * cosf) * c_l) * mat->diffuse;
-                        a0 = ((pdf * cosf) * c_0) * mat->diffuse;
-                        bterm = pow(fabs(dot(w_o, refl)), mat->smoothness) * (mat->reflection / dot(w_i, mk(0.0, 0.0, 1.0)));
-                    }
-                } else if (kind == 3) {  // smooth_transparent_dialectric.rs:79-95
-                    a = (pdf * cosf) * dielectric_strength(fr, w_o);
-                    a0 = (pdf * cosf) * dielectric_strength(dielectric_fresnel(mat, w_i, 0.0), w_o);
-                    bterm = 0.0;
-                } else {  // lambertian_material.rs:27-34
-                    a = ((pdf * cosf) * c_l) * mat->diffuse;
-                    a0 = ((pdf * cosf) * c_0) * mat->diffuse;
-                    bterm = 0.0;
-                }
+                if (kind == 3) dielectric_factors<false>(mat, fr, w_i, w_o, pdf, cosf, a, a0, bterm);
+                else level_factors<3>(mat, kind, w_i, w_o, pdf, cosf, c_l, c_0, a, a0, bterm, cut);
                 // (render_kernel's shade(): levels below a cut one are traced and change nothing)
                 if (!(flags & kPathCut)) {
                     Acc = Acc + T * bterm;
@@ -251,11 +163,8 @@ __global__ __launch_bounds__(256) void integrate_kernel(IntegrateArgs A) {
                 if (cut) flags |= kPathCut;
                 wo_y = wo_world.y;  // the sky term reads the un-normalised direction's y
             }
-            // Ray::new(location, w_o).bias(1e-7): normalise, step, normalise again (mod.rs:41-61)
-            const V3 d1 = normalize_n1(wo_world);  // an orthonormal basis applied to a unit vector
             ++bounces;
-            ray.o = add(h.loc, scl(d1, kBounceBias));
-            ray.d = normalize_n1(d1);
+            bounce_ray(h, wo_world, ray.o, ray.d);
         } while (false);
         if (fin) {
             // the caller reads them: plain 16-B and 8-B stores
