@@ -49,7 +49,7 @@ def test_abi_version_and_error_strings():
 def test_wide_offset_limits():
     """The default kernels address triangles (80-B TriVerts) and 4-wide nodes (128 B) with 32-bit
     byte offsets; past 4 GB of triangles or 2^25 wide nodes a scene takes the 64-bit-offset kernels
-    (vr_render.hip render_kernel<.., BIG>; ADVICE r04: before, such a mesh silently read the wrong
+    (vr_render_kernel.h render_kernel<.., BIG>; ADVICE r04: before, such a mesh silently read the wrong
     records).  Host only: the choice, at and either side of both limits."""
     f = N.lib().vr_scene_needs_wide_offsets
     tri_limit = (1 << 32) // 80 + 1  # the first count whose last record's offset reaches 2^32

@@ -1,5 +1,5 @@
 """The camera lens (VR_HAS_CAMERA_LENS) on the device: the render kernel's camera step under a lens (the
-CAM = 2 instantiations of vanrijn_amd/csrc/vr_render.hip), camera_rays_kernel and the block cull.
+CAM = 2 instantiations of vanrijn_amd/csrc/vr_render_kernel.h), camera_rays_kernel and the block cull.
 
 The chain of evidence, as tests/test_gpu_camera_pose.py builds it for the pose:
   1. a lens of radius 0 set explicitly changes no bit and not the kernel;

@@ -1,5 +1,5 @@
 """The camera pose (VR_HAS_CAMERA_POSE) on the device: the render kernel's camera step (the POSED
-instantiations of vanrijn_amd/csrc/vr_render.hip), camera_rays_kernel and the block cull under a pose.
+instantiations of vanrijn_amd/csrc/vr_render_kernel.h), camera_rays_kernel and the block cull under a pose.
 
 The chain of evidence:
   1. the default pose set explicitly changes no bit, and is the oracle's ImageSampler;

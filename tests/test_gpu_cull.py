@@ -1,6 +1,6 @@
 """Camera-frustum culling of 8x8 pixel blocks changes no bit of the accumulation records.
 
-block_cull_kernel (vr_render.hip) marks the blocks of a launch's tile whose camera rays all miss
+block_cull_kernel (vr_cull.hip) marks the blocks of a launch's tile whose camera rays all miss
 every object by a wide margin; the render kernel skips their work items and the ordered reduce
 applies their samples as the missed camera ray's photon {0, 0} (camera.rs:110-113) without staged
 data.  The records must equal a render with the test off (VR_LAUNCH_NO_CULL), on a full frame, on a

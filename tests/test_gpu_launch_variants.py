@@ -6,7 +6,7 @@
   rule"): the tie scenes (test_gpu_ties.py) and the tie / flat meshes of test_gpu_build.py are decided
   here with the culling off, against the oracle's reference mode -- the later in-order leaf wins inside
   a BVH (bvh.rs:77-92), the earlier object across objects (sampler.rs:9-20).
-* VR_LAUNCH_NO_COOP: the cooperative tail (vr_render.hip coop_step, the COOP instantiations small
+* VR_LAUNCH_NO_COOP: the cooperative tail (vr_render_kernel.h coop_step, the COOP instantiations small
   launches of mirror scenes take) against the plain kernel, bit for bit, on the C1 scene
   (benches/simple_scene.rs), whose paths trapped between mirror facets run to the 128-bounce limit.
 * VR_SCENE_WIDE_OFFSETS: the 64-bit-offset kernels that scenes past 4 GB of triangles or 2^25 wide

@@ -121,7 +121,7 @@ def test_megakernel_matches_the_oracle(regime, scene_of, oracle):
     without the absolute term passes here).  test_sphere_field_matches_the_oracle decides that margin.
     At (1e20, 0), (3e34, 0) and (1e36, 0) every path stays trapped on its surface to the recursion
     limit, through levels whose shading is NaN: where the kernels' forward product must discard what the
-    reference discards (vr_render.hip shade(), kPathCut)."""
+    reference discards (vr_render_kernel.h shade(), kPathCut)."""
     scene, orc = scene_of(regime, oracle)
     ref = orc.render_samples(TILE, H, W, SPP, seed=SEED, mode=oracle.MODE_REFERENCE, nthreads=8)
     assert (ref["flags"] & 1).sum() >= 3000

@@ -1,4 +1,4 @@
-"""The single-BVH render kernels of one material kind look a path's wavelength up once (vr_render.hip PATHWL).
+"""The single-BVH render kernels of one material kind look a path's wavelength up once (vr_render_kernel.h PATHWL).
 
 Where lambda is drawn, at the camera hit, they find its segment and ratio on the wavelength grid the scene's
 material rows share (vr_device.h path_segment); the surface colour of every later hit and the sky at the

@@ -1,4 +1,4 @@
-"""The trimmed node step and leaf append of the render kernel's traversal loop (vr_render.hip phase B).
+"""The trimmed node step and leaf append of the render kernel's traversal loop (vr_render_kernel.h phase B).
 
 The leaf append tells a queued leaf by one unsigned compare on the hit child's link, (uint32_t)link >
 0x80000000u: negative and not the empty slot's INT32_MIN.  An empty slot's link alone keeps it off the stack

@@ -3,7 +3,7 @@
 closest_intersection keeps the later in-order leaf on equal distances inside a BVH
 (bounding_volume_hierarchy.rs:77-92) and sampler.rs:9-20 keeps the earlier object across objects.
 The kernel tests queued leaves on any lane of the wave and merges each ray's candidates through LDS
-atomics (vr_render.hip leaf_round), so the winner must not depend on which lane tested what or in
+atomics (vr_render_kernel.h leaf_round), so the winner must not depend on which lane tested what or in
 which order.  Every triangle here is present two or three times at exactly the same place (equal
 distances for every ray) with different shading normals, and a second BVH object repeats part of
 the mesh: the winner's normal steers the bounce, so a wrong tie-break changes bounce counts,

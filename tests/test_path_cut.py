@@ -3,7 +3,7 @@
 The reference returns from the innermost level outward: I_k = bsdf_k(I_{k+1} pdf_k |cos_k|), an
 affine map a_k I_{k+1} + b_k -- except that a mirror or Phong surface met from behind returns the
 constant 0 without reading I_{k+1} (reflective_material.rs:20-24, phong_material.rs:19-21).  The
-kernels (vr_render.hip shade(), vr_integrate.hip) accumulate outward-in, Acc += T b_k, T *= a_k, and
+kernels (vr_render_kernel.h shade(), vr_integrate.hip) accumulate outward-in, Acc += T b_k, T *= a_k, and
 a cut level used to be a_k = b_k = 0 like any other: a NaN below it (a bounce ray that re-hits its
 own surface at distance 0 -- every trapped path of a scene scaled by 1e20, tests/test_gpu_magnitudes.py)
 then made T = 0 * NaN where the reference has discarded it.  Found on the device at (1e20, 0),

@@ -1,7 +1,8 @@
 """Static VALU cost of the render kernel per code section (analysis aid).
 
-Builds vr_render.hip to assembly with the product build's flags and -DVR_MARKS (asm ';@mark <name>'
-comments at the section starts of vr_render.hip), takes one instantiation of render_kernel, selected by
+Builds the camera unit of the instantiation asked for (vr_render_cam<CAM>.hip) to assembly with the product
+build's flags and -DVR_MARKS (asm ';@mark <name>' comments at the section starts of vr_render_kernel.h),
+takes that instantiation of render_kernel, selected by
 its template arguments, attributes every instruction to the last marker above it in layout order, and
 prices each instruction with a simple gfx950 issue model (wave64: f32 / int VALU 2 cycles, f64 and 64-bit
 ops 4, f64 transcendentals 16, 32-bit integer multiplies 8).  The kernel's resources (VGPRs, SGPRs,
@@ -13,9 +14,9 @@ Lambertian-only, DARK0, 16-bit stack entries, the default camera, the single-BVH
 --keep: leave the assembly there.  An older source, whose kernel has fewer template parameters, is
 matched on the parameters it has."""
 import collections
+import importlib.util
 import os
 import re
-import subprocess
 import sys
 import tempfile
 
@@ -32,6 +33,32 @@ DEFAULTS = {"MATS": 3, "MINW": 3, "WHITTED": 0, "COOP": 0, "BIG": 0, "S16": 0, "
 # the C3 timed kernel
 C3 = {"STACK": 32, "COUNT": 0, "RECORD": 0, "DARK0": 1, "MATS": 1, "MINW": 3, "WHITTED": 0, "COOP": 0, "BIG": 0,
       "S16": 1, "CAM": 0, "ONE": 1}
+# the units besides the render units that hold a kernel vr_render.hip once held
+MOVED_SOURCES = ["vr_reduce.hip", "vr_cull.hip", "vr_query.hip"]
+
+
+def product_build():
+    """vanrijn_amd/build.py as a module: its flags, unit lists and capped parallel compile, without importing
+    the package (which loads the library)"""
+    spec = importlib.util.spec_from_file_location("vr_build", os.path.join(ROOT, "vanrijn_amd", "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def device_assembly(out, extra, sources=None):
+    """The device assembly of `sources` (paths), or of every unit that holds a kernel of the render launch, the
+    ray trace or the reduce, with the product build's flags (the scheduler options change the code) and then
+    `extra`: compiled in parallel under the build's cap, concatenated into `out`."""
+    vb = product_build()
+    if sources is None:
+        sources = [os.path.join(vb.CSRC, s) for s in vb.RENDER_SOURCES + MOVED_SOURCES]
+    with tempfile.TemporaryDirectory() as tmp:
+        parts = vb.compile_units(sources, tmp, vb.compile_flags_of() + ["--cuda-device-only", "-S"] + extra, ".s",
+                                 quiet=True)
+        with open(out, "w") as f:
+            for part in parts:
+                f.write(open(part).read())
 
 
 def kernel_args(name):
@@ -114,7 +141,7 @@ def cost(op):
 
 def main():
     argv = sys.argv[1:]
-    want, asm, keep, src = dict(C3), None, None, os.path.join(ROOT, "vanrijn_amd/csrc/vr_render.hip")
+    want, asm, keep, src = dict(C3), None, None, None
     extra = []
     while argv:
         a = argv.pop(0)
@@ -130,11 +157,9 @@ def main():
             extra.append(a)
     if asm is None:
         asm = keep or os.path.join(tempfile.mkdtemp(), "render.s")
-        # the product build's compile flags (vanrijn_amd/build.py FLAGS): the scheduler options change the code
-        flags = subprocess.check_output([sys.executable, os.path.join(ROOT, "vanrijn_amd/build.py"), "--print-flags"],
-                                        text=True).split()
-        subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["--cuda-device-only", "-S", "-DVR_MARKS"] + extra +
-                              [src, "-o", asm], stderr=subprocess.DEVNULL)
+        if src is None:  # the one unit that holds the instantiation
+            src = os.path.join(ROOT, "vanrijn_amd/csrc/vr_render_cam%d.hip" % want["CAM"])
+        device_assembly(asm, ["-DVR_MARKS"] + extra, [src])
     text = open(asm).read()
     bodies = kernel_bodies(text)
     names = [n for n in bodies if kernel_args(n) == want]

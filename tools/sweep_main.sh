@@ -1,6 +1,6 @@
 #!/bin/bash
 # One-dimensional sweeps of the render kernel's tuning knobs around the defaults, main.rs scene
-# 1024^2 @256 (tuning build: bash tools/build_variant.sh tune -DVR_TUNING_VARIANTS; abx/libtune.so).
+# 1024^2 @256 (tuning build: python -m vanrijn_amd.build --out abx/libtune.so -DVR_TUNING_VARIANTS).
 #   bash tools/sweep_main.sh [scene spp size]
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"

@@ -1,5 +1,5 @@
 // vr_camera.h -- the camera ray rule, and the lens rule below it, shared by the render kernel's camera
-// step (vr_render.hip), the block cull beside it, camera_rays_kernel (vr_integrate.hip) and the host's
+// step (vr_render_kernel.h), the block cull (vr_cull.hip), camera_rays_kernel (vr_integrate.hip) and the host's
 // vr_camera_ray / vr_camera_lens_ray: one definition, so all four form the same bits.
 //
 // ImageSampler (camera.rs:24-66) looks down +z from `location` with the film one unit away.  A pose

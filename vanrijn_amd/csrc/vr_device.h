@@ -1,4 +1,4 @@
-// vr_device.h -- device-side building blocks of the gfx950 path tracer (included by vr_render.hip).
+// vr_device.h -- device-side building blocks of the gfx950 path tracer (included by every device unit).
 //
 // f64 vector math, the counter-based random stream, spectra and CIE matching, the reference's
 // exact line-slab test, ray-triangle / sphere / plane tests, closest-hit traversal and hit
@@ -518,7 +518,7 @@ __device__ __forceinline__ void slab32_flags(const float* b, const Ray32& r, flo
 //    can appear and the NaN-ignoring max3 / min3 may drop another operand than the pairwise form,
 //    so lo / hi can differ.  But sure = (d < -inf) is false and maybe = !(d > inf) is true whatever
 //    lo and hi are, and the cull thresholds carry E = inf (cull_far = +inf, cull_behind = -inf:
-//    margin_of(), vr_render.hip set_cull_far), so nothing is culled in either form: every live child
+//    margin_of(), vr_render_kernel.h set_cull_far), so nothing is culled in either form: every live child
 //    is taken and sent to the exact test.  Only the visiting order, which is work and not results
 //    (DESIGN.md section 5), can differ.
 __device__ __forceinline__ void slab32_ordered(float near_x, float near_y, float near_z, float far_x, float far_y,

@@ -32,7 +32,7 @@ static bool needs_big_offsets(uint64_t tri_count, uint64_t wide_count) {
 // rows lie on different wavelength grids runs it too (VR_CHOICE_OWN_GRIDS), and a launch small enough for the
 // cooperative tail keeps the kernels it had, with the tail or (VR_LAUNCH_NO_COOP) without it, so that
 // flag's A/B still isolates the tail.  It exists with 16-bit stack entries in the 24 and 32 stack classes
-// and with 32-bit ones in the 32 class (vr_render.hip launch_render_t).
+// and with 32-bit ones in the 32 class (vr_render_kernel.h launch_render_t).
 static bool takes_one_bvh(uint64_t bvh_count, int32_t root4, uint32_t other, int stack_depth, bool s16) {
     if (bvh_count != 1 || root4 < 0 || other != 0) return false;
     return s16 ? stack_depth <= 32 : (stack_depth > 24 && stack_depth <= 32);
@@ -60,7 +60,7 @@ static vr::LaunchChoice launch_choice(const vr_scene* s, bool coop, bool gated, 
     lc.big = s->force_big || needs_big_offsets(s->tri_count, s->wide_count);
     // the cooperative tail's instantiations exist for DARK0 scenes with a reflective material
     lc.coop = coop && !recording && !counting && !lc.big && s->dev.integrator != 1 && s->dark0 && (lc.mats & 2);
-    // 16-bit LDS stack entries: every node index of the tree fits (round 6, vr_render.hip
+    // 16-bit LDS stack entries: every node index of the tree fits (round 6, vr_render_kernel.h
     // launch_render_t; VR_LAUNCH_STACK32 keeps 32-bit entries, the same records bit for bit)
     lc.s16 = !recording && !counting && !lc.big && !lc.coop && s->dev.integrator != 1 && s->wide_count < 65536 &&
              stack <= 32 && !(launch_flags & VR_LAUNCH_STACK32);
@@ -69,7 +69,7 @@ static vr::LaunchChoice launch_choice(const vr_scene* s, bool coop, bool gated, 
                            (lc.big ? VR_CHOICE_WIDE_OFFSETS : 0u) |
                            ((launch_flags & VR_LAUNCH_MULTI_BVH) ? VR_CHOICE_MULTI_BVH : 0u) |
                            // the single-BVH kernels of one material kind look a path's wavelength up once,
-                           // on the one grid every row shares (vr_render.hip PATHWL)
+                           // on the one grid every row shares (vr_render_kernel.h PATHWL)
                            (lc.dark0 && (lc.mats == 1 || lc.mats == 2) && !s->grid_shared ? VR_CHOICE_OWN_GRIDS : 0u);
     lc.one_bvh = takes_one_bvh(s->bvhs.size(), s->bvhs.empty() ? INT32_MIN : s->bvhs[0].root4, other, stack, lc.s16);
     return lc;
@@ -142,7 +142,7 @@ int ctx_acquire(vr_scene* s, CallCtx** out, const hipStream_t* want = nullptr) {
     // blocking sync: a host-buffer call waits on `done` asleep, not spinning a core (8 spinning
     // callers under a 16-CPU quota throttled the whole process for ~10 ms at a time)
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->done, hipEventDisableTiming | hipEventBlockingSync);
-#ifdef VR_COOP_PROF  // analysis builds: per-wave records after word 24 (vr_render.hip)
+#ifdef VR_COOP_PROF  // analysis builds: per-wave records after word 24 (vr_render_kernel.h)
     if (e == hipSuccess) e = hipMalloc(&c->queue, 65536);
     if (e == hipSuccess) e = hipMemsetAsync(c->queue, 0, 65536, c->stream);
 #else
@@ -260,7 +260,7 @@ vr::RenderArgs make_args(const vr_scene* s, const vr_render_params* p, double* s
     a.leaf_stall = ls ? (uint32_t)std::max(1, atoi(ls)) : 3u;
     const char* lf = tuning_env("VR_LEAF_FEW");  // tuning hook (0: off)
     a.leaf_few = lf ? (uint32_t)std::max(0, atoi(lf)) : 0u;
-    // the cooperative tail (vr_render.hip coop_step, the COOP instantiations): launches of at most
+    // the cooperative tail (vr_render_kernel.h coop_step, the COOP instantiations): launches of at most
     // 4 M pixel-samples (a small frame's time is its longest paths') of scenes with a reflective
     // material (paths trapped between mirror facets run to the 128-bounce limit: C1,
     // benches/simple_scene.rs).  Scenes without mirrors never take it: on main.rs's Lambertian scene
@@ -496,7 +496,7 @@ int enqueue_passes(vr_scene* s, CallCtx* c, const vr_render_params* p, double* s
         a.records = records;
         a.counters = counters;
         a.wg_times = done == 0 ? wg_times : nullptr;
-#ifdef VR_COOP_PROF  // analysis builds: the previous launch's tail-wave sums (vr_render.hip)
+#ifdef VR_COOP_PROF  // analysis builds: the previous launch's tail-wave sums (vr_render_kernel.h)
         {
             static unsigned long long h[16 + 6000];
             VR_HIP(hipStreamSynchronize(st));

@@ -10,7 +10,7 @@
 //
 // Traversal is vr_walk4.h's per-lane walk of the 4-wide tree (closest hit for path rays, any hit for
 // the Whitted shadow rays, on the same LDS stack).  One shading level is vr_shade.h's, the functions
-// render_kernel's `shade` lambda calls too (vr_render.hip), with the general lambda-0 pair (T0, Acc0)
+// render_kernel's `shade` lambda calls too (vr_render_kernel.h), with the general lambda-0 pair (T0, Acc0)
 // and every material kind compiled in; the path state and the transitions around a level are that
 // kernel's restated for one lane, the same operations in the same order: under -ffp-contract=off the
 // photons equal the megakernel's bit for bit.

@@ -1,6 +1,6 @@
 // vr_layout.h -- HBM layout of a flattened scene and the kernel parameter blocks.
 //
-// Shared by the host side (vr_scene.cpp, vr_capi.cpp) and the gfx950 kernels (vr_render.hip).
+// Shared by the host side (vr_scene.cpp, vr_capi.cpp) and the gfx950 kernels (every device unit).
 // Sizes are chosen for 64-lane waves doing independent per-lane gathers: every record a lane
 // reads whole is a multiple of 16 B and 16-B aligned so it is fetched with dwordx4 loads.
 #pragma once
@@ -225,7 +225,7 @@ struct RenderArgs {
     const uint32_t* live_blocks;
     const uint32_t* live_count;
     // 1: the sky row lies on the wavelength grid the material rows share (materials[0]'s; vr_host_scene.cpp
-    // update_grid_shared), so a path's segment and ratio serve the sky lookup too (vr_render.hip PATHWL)
+    // update_grid_shared), so a path's segment and ratio serve the sky lookup too (vr_render_kernel.h PATHWL)
     uint32_t sky_on_grid;
     uint32_t reserved32;
     uint64_t reserved[3];  // unused: keeps the kernel-argument offsets of the members below (moving them moves spills)
@@ -233,8 +233,8 @@ struct RenderArgs {
     // staged photon the launch's generation, which the ordered reduce checks before reading it
     uint32_t* stage_tag;  // [pass sample][tile pixel], or nullptr
     uint32_t stage_gen;   // this pass's generation (never 0)
-    // 1: the scene's pose is not the default one and the camera step loads it (vr_render.hip
-    // load_pose_args); 0: the step forms normalize((x, y, 1)), which the rule gives for the default pose;
+    // 1: the scene's pose is not the default one and the camera step loads it (vr_render_kernel.h
+    // posed_direction); 0: the step forms normalize((x, y, 1)), which the rule gives for the default pose;
     // 2: the scene has a lens (lens_radius != 0) and the step applies pose and lens, whatever the pose
     uint32_t posed;
 };
@@ -319,9 +319,11 @@ enum Counter : int {
     kCntCount = 36
 };
 
-// Launch wrappers implemented in vr_render.hip (host-callable).
-// Which render_kernel instantiation a launch runs (vr_host.cpp enqueue_passes picks, vr_render.hip
-// launch_render maps it to the template).
+// Launch wrappers implemented in the device units (host-callable): vr_render_launch.hip launch_render;
+// vr_cull.hip the block cull and compact; vr_reduce.hip launch_accumulate; vr_query.hip launch_trace and
+// launch_query.
+// Which render_kernel instantiation a launch runs (vr_host.cpp enqueue_passes picks; launch_render and
+// vr_render_kernel.h launch_render_t map it to the template).
 struct LaunchChoice {
     int stack_depth;  // LDS stack entries the scene's traversal needs (class 24 / 32 / 48)
     bool counting;    // the counting variant (VR_LAUNCH_COUNTERS)
@@ -375,7 +377,7 @@ int launch_query(const QueryArgs& args, int stack_depth, int grid_limit, void* s
 // -1000: deeper than the largest stack class
 int launch_integrate(const IntegrateArgs& args, int stack_depth, int grid_limit, void* stream);
 int launch_camera_rays(const CameraRaysArgs& args, void* stream);
-// vr_render.hip: the ordered reduce alone -- update_pixel of photons[s * npix + p], s < spp, into the
+// vr_reduce.hip: the ordered reduce alone -- update_pixel of photons[s * npix + p], s < spp, into the
 // records at `state` (RenderArgs::state's layout), no cull mask
 int launch_accumulate(double* state, const double* photons, uint64_t npix, uint32_t spp, uint32_t accumulate,
                       void* stream);

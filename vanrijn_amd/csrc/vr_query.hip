@@ -96,6 +96,39 @@ __global__ __launch_bounds__(256) void query_kernel(QueryArgs A) {
     }
 }
 
+template <int STACK>
+__global__ __launch_bounds__(256) void trace_kernel(TraceArgs A) {
+    __shared__ int st_node[STACK * 256];
+    __shared__ float st_t[STACK * 256];
+    const int tid = threadIdx.x;
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + tid;
+    if (i >= A.n) return;
+    Ray r;
+    r.o = ldv(A.origins + 3 * i);
+    r.d = ldv(A.directions + 3 * i);
+    RayPre pre = prepare(r);
+    Counts cnt = {0, 0, 0, 0, 0, 0, 0, 0};
+    Best best = closest_hit<STACK, false>(A.scene, pre, st_node, st_t, tid, cnt);
+    vr_hit_record* out = (vr_hit_record*)A.out + i;
+    out->valid = best.kind != kNone;
+    if (!best.kind) return;
+    HitInfo h;
+    hit_info(A.scene, best, pre, h);
+    out->object = best.object;
+    out->primitive = best.kind == kPrim ? A.scene.prims[best.index].position : best.index;
+    if (best.kind == kTri) {
+        for (int b = 0; b < A.scene.bvh_count; ++b)
+            if (A.scene.bvhs[b].object == best.object)
+                out->primitive = A.scene.tris[best.index].rank - A.scene.bvhs[b].tri_base;  // reference leaf position
+    }
+    out->distance = best.d;
+    out->location[0] = h.loc.x; out->location[1] = h.loc.y; out->location[2] = h.loc.z;
+    out->normal[0] = h.normal.x; out->normal[1] = h.normal.y; out->normal[2] = h.normal.z;
+    out->tangent[0] = h.tangent.x; out->tangent[1] = h.tangent.y; out->tangent[2] = h.tangent.z;
+    out->cotangent[0] = h.cotangent.x; out->cotangent[1] = h.cotangent.y; out->cotangent[2] = h.cotangent.z;
+    out->retro[0] = h.retro.x; out->retro[1] = h.retro.y; out->retro[2] = h.retro.z;
+}
+
 }  // namespace dev
 
 template <int STACK>
@@ -121,6 +154,17 @@ int launch_query(const QueryArgs& a, int stack_depth, int grid_limit, void* stre
     if (stack_depth <= 24) launch_query_t<24>(a, grid, s);
     else if (stack_depth <= 32) launch_query_t<32>(a, grid, s);
     else launch_query_t<48>(a, grid, s);
+    return (int)hipGetLastError();
+}
+
+int launch_trace(const TraceArgs& a, int stack_depth, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (a.n == 0) return 0;
+    dim3 grid((unsigned)((a.n + 255) / 256)), block(256);
+    if (stack_depth <= 24) hipLaunchKernelGGL(dev::trace_kernel<24>, grid, block, 0, s, a);
+    else if (stack_depth <= 32) hipLaunchKernelGGL(dev::trace_kernel<32>, grid, block, 0, s, a);
+    else if (stack_depth <= 48) hipLaunchKernelGGL(dev::trace_kernel<48>, grid, block, 0, s, a);
+    else return -1000;
     return (int)hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-// vr_render.hip -- the MI355X (gfx950) hot path: camera rays, closest-hit BVH traversal,
+// vr_render_kernel.h -- the MI355X (gfx950) hot path: camera rays, closest-hit BVH traversal,
 // ray-triangle / sphere / plane tests, the SimpleRandomIntegrator path loop, Lambertian and
 // reflective BSDFs and the Kahan-compensated CIE-XYZ accumulation, in one kernel.
 //
@@ -22,6 +22,11 @@
 //   * each sample's final photon {wavelength, intensity} goes to a staging buffer;
 //     accumulate_kernel turns it into XYZ and folds the samples of a pixel in sample order with
 //     the reference's Kahan update_pixel, so the buffers are bit-identical to sequential calls.
+//
+// Included by the three camera units (vr_render_cam0.hip, vr_render_cam1.hip, vr_render_cam2.hip): each
+// instantiates launch_render_class for one camera mode and with it that mode's render kernels, which
+// no other mode shares; vr_render_launch.hip's launch_render picks among them.
+#pragma once
 #include <hip/hip_runtime.h>
 
 #include <float.h>
@@ -1619,400 +1624,11 @@ __global__ __launch_bounds__(256, MINW) void render_kernel(RenderArgs A, const P
 #undef VR_STAMP
 #undef VR_SEC
 
-// Camera-frustum test of the tile's 8x8 pixel blocks (one thread per block).  The camera rays of a
-// block start at the camera and pass through the film rectangle its pixels' sample squares cover
-// (camera.rs:24-66: x = (col + u) fw/w - fw/2, y = (h - row - 1 + v) fh/h - fh/2, u, v in [0, 1),
-// direction d(x, y) = x right + y up + film_distance forward normalised: vr_camera.h's rule, so
-// (x, y, 1) under the default pose).  d is affine in (x, y), so the block's directions are the
-// parallelogram spanned by d at the rectangle's four corners, in world space, where every test
-// below is made.  A block is culled only when every such line provably misses every object, with
-// margins far beyond the f64 rounding of the reference's tests:
-//  * a plane (plane.rs:49-75): its t = num / dn is negative for every ray -- num and n . d
-//    of opposite signs at all four corners of the rectangle (n . d is affine on the parallelogram:
-//    its extremes are at the corners), each by more than 1e-9 of its magnitude scale;
-//  * a BVH root box (a ray that misses the box misses every triangle in it) wholly in front of the
-//    camera: its corners p - location in camera coordinates (p . right, p . up, p . forward) =: (px,
-//    py, pz); the directions that reach the box have (x, y) / film_distance inside the bounding
-//    rectangle of the corners' (px / pz, py / pz), which, widened, misses the block's film
-//    rectangle divided by film_distance.  The dot products apply the basis' transpose where its
-//    inverse is meant.  vr_scene_set_camera_pose admits a basis B = [right up forward] with
-//    |B^T B - I| <= 1e-9 per entry, so with w = (x, y, film_distance) the computed triple is
-//    t (w + E w), |E w|_i <= 1e-9 (|x| + |y| + film_distance), and px / pz is off x / film_distance
-//    by at most 1e-9 s^2 (1 + 1e-9 s), s = 1 + (|x| + |y|) / film_distance: the rectangle is widened
-//    by 1e-6 s^2 with s from the computed bounds, a thousand times that and the f64 rounding of the
-//    dot products (the front test leaves |px|, |py| <= 1e6 pz, so 1e-9 s stays below 1e-2);
-//  * a sphere, or a root box through its bounding sphere: the camera is outside it and the angle
-//    between the sphere's centre and the axis of the block's cone of directions exceeds the cone's
-//    half-angle (attained at a corner) plus the sphere's angular radius plus 1e-6 rad.  A cone of
-//    half-angle below 90 degrees is convex, so holding the four corner directions it holds every
-//    positive combination of them: every direction of the block (a wider cone is not used).
-// Under a lens (vr_camera.h: the lens rule) a sample's ray leaves the lens point o' = o + a right + b up,
-// |(a, b)| <= lens_radius * |disc| with |disc| <= 1 + a few ulp, and its direction is the pinhole
-// direction of the film point (x - a k, y - b k), k = film_distance / focus_distance.  With rho =
-// lens_radius (1 + 1e-6) -- the disc's excess, the products' rounding and the 1e-9 the basis may be off
-// orthonormal (|a right + b up| <= |(a, b)| sqrt(1 + 2e-9)) a hundred times over -- two widenings
-// carry every test over, and with lens_radius 0 every number below is what it was:
-//  * directions: the block's film rectangle grows by rho k on each side before the corner directions
-//    are formed, so the parallelogram and the cone hold every lens ray's direction;
-//  * origins: a ray from o' that meets a sphere (c, r) runs within |o' - o| <= rho of the same
-//    direction's ray from o, which then meets the sphere (c, r + rho): spheres, and boxes' bounding
-//    spheres, are tested from o with their radius inflated by rho.  A plane's num from o' is off its
-//    value from o by (o' - o) . n, at most rho |n|: |num| must exceed its tolerance plus rho |n|, and
-//    then keeps its sign over the lens.  A box corner seen from o' has camera coordinates (px - a', py
-//    - b', pz - c') with |a'|, |b'| <= rho and |c'| <= 1e-6 lens_radius (a right . forward + b up .
-//    forward, at most 2e-9 of it): the front test must hold for the smallest pz and the largest |px|,
-//    |py|, and the bounding rectangle takes each corner's extremes (px +- rho) / pz over both ends of
-//    pz's range (a quotient monotone in pz takes its extremes there).
-// A lens so wide that nothing can be proved -- a cone past 90 degrees, corner directions on both sides
-// of every plane -- leaves every block live: slower, never wrong.
-// Each sample of a culled block is then exactly the missed camera ray's photon {0, 0}, whatever
-// its random draws.
-__device__ __forceinline__ double vr_angle(V3 a, V3 b) {
-    return atan2(sqrt(dot(cross(a, b), cross(a, b))), dot(a, b));
-}
-__global__ __launch_bounds__(256) void block_cull_kernel(RenderArgs A, const Prim* prims, const Bvh* bvhs,
-                                                         uint8_t* mask, PoseArgs pose, LensArgs lens) {
-    const uint32_t bw = (uint32_t)((A.tile_width + 7) / 8), bh = (uint32_t)((A.tile_height + 7) / 8);
-    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= bw * bh) return;
-    const uint32_t bx = b % bw, by = b / bw;
-    const double c0 = (double)(A.start_column + 8 * (uint64_t)bx);
-    const double c1 = (double)(A.start_column + min((uint64_t)8 * bx + 8, A.tile_width));
-    const double r0 = (double)(A.start_row + 8 * (uint64_t)by);
-    const double r1 = (double)(A.start_row + min((uint64_t)8 * by + 8, A.tile_height));
-    const double H = (double)A.height;
-    const double xa = c0 * A.film[0] - A.film[1], xb = c1 * A.film[0] - A.film[1];
-    const double ya = (H - r1) * A.film[2] - A.film[3], yb = (H - r0) * A.film[2] - A.film[3];
-    const double mx = 1e-9 * (fabs(xa) + fabs(xb) + 1.0), my = 1e-9 * (fabs(ya) + fabs(yb) + 1.0);
-    const DeviceScene& S = A.scene;
-    const double fd = pose.film_distance;
-    // the lens: rho bounds the lens point's distance from the location, rho k the film point's shift
-    const double rho = lens.lens_radius * (1.0 + 1e-6), dz = 1e-6 * lens.lens_radius;
-    const double lw = rho * (fd / lens.focus_distance);
-    const double xlo = (fmin(xa, xb) - mx) - lw, xhi = (fmax(xa, xb) + mx) + lw;
-    const double ylo = (fmin(ya, yb) - my) - lw, yhi = (fmax(ya, yb) + my) + lw;
-    const V3 R = ldv(pose.right), U = ldv(pose.up), F = ldv(pose.forward);
-    // the rule at the rectangle's corners: the block's directions in world space, not normalised
-    V3 pc[4];
-    for (int k = 0; k < 4; ++k) {
-        const camera::Vec d =
-            camera::film_to_world(pose.right, pose.up, pose.forward, fd, (k & 1) ? xhi : xlo, (k & 2) ? yhi : ylo);
-        pc[k] = mk(d.x, d.y, d.z);
-    }
-    V3 axis = mk(0.0, 0.0, 0.0);
-    for (int i = 0; i < 4; ++i) axis = add(axis, normalize(pc[i]));
-    axis = normalize(axis);
-    double half = 0.0;
-    for (int i = 0; i < 4; ++i) half = fmax(half, vr_angle(axis, pc[i]));
-    const bool convex = half < 1.5;  // a cone below 90 degrees (1.5708 rad) bounds its corners' hull
-    const V3 o = mk(S.camera[0], S.camera[1], S.camera[2]);
-    // a sphere (centre c, radius r) every ray of the block misses
-    auto sphere_clear = [&](V3 c, double r0) {
-        const double r = r0 + rho;  // the lens' origins (above)
-        const V3 v = sub(c, o);
-        const double dist = sqrt(dot(v, v));
-        if (!convex || !(dist > r * (1.0 + 1e-6) + 1e-9)) return false;
-        return vr_angle(axis, v) > half + asin(fmin(1.0, r / dist)) + 1e-6;
-    };
-    bool clear = true;
-    for (int i = 0; i < A.scene.prim_count && clear; ++i) {
-        const Prim& pr = prims[i];
-        const V3 c = ldv(pr.vec);
-        if (pr.kind == 0) {
-            const V3 q = ldv(pr.pre);
-            const double num = dot(sub(q, o), c);
-            const double nn = sqrt(dot(c, c));
-            const double tol = 1e-9 * nn * (sqrt(dot(q, q)) + sqrt(dot(o, o)) + 1.0);
-            if (!(fabs(num) > tol + rho * nn)) {
-                clear = false;
-                break;
-            }
-            for (int k = 0; k < 4; ++k) {
-                const double dn = dot(pc[k], c);
-                const double t = 1e-9 * nn * sqrt(dot(pc[k], pc[k]));
-                if (!(num > 0.0 ? dn < -t : dn > t)) clear = false;
-            }
-        } else {
-            clear = sphere_clear(c, pr.scalar);
-        }
-    }
-    for (int i = 0; i < A.scene.bvh_count && clear; ++i) {
-        const Bvh& bv = bvhs[i];
-        if (bv.root4 == INT32_MIN) continue;  // an empty mesh never hits
-        const double* bb = bv.root_box;
-        // a box wholly in front of the camera, in camera coordinates: the directions that reach it
-        // project (px/pz, py/pz) into the bounding rectangle of its corners' projections; clear
-        // when that rectangle, widened, misses the block's film rectangle over film_distance
-        double ulo = INFINITY, uhi = -INFINITY, vlo = INFINITY, vhi = -INFINITY;
-        bool front = true;
-        for (int k = 0; k < 8; ++k) {
-            const V3 p = mk(bb[k & 1] - o.x, bb[2 + ((k >> 1) & 1)] - o.y, bb[4 + (k >> 2)] - o.z);
-            const double px = dot(p, R), py = dot(p, U), pz = dot(p, F);
-            const double pzl = pz - dz, pzh = pz + dz;  // pz over the lens' origins; pz itself without a lens
-            front = front && pzl > 1e-6 * ((fabs(px) + rho) + (fabs(py) + rho) + fabs(pz));
-            ulo = fmin(ulo, fmin((px - rho) / pzl, (px - rho) / pzh));
-            uhi = fmax(uhi, fmax((px + rho) / pzl, (px + rho) / pzh));
-            vlo = fmin(vlo, fmin((py - rho) / pzl, (py - rho) / pzh));
-            vhi = fmax(vhi, fmax((py + rho) / pzl, (py + rho) / pzh));
-        }
-        if (front) {
-            // the margin: 1e-6 s^2 covers the transpose standing in for the inverse of a basis that
-            // is orthonormal to 1e-9 (at most 1e-9 s^2 (1 + 1e-9 s), see above) a thousand times over
-            const double s = fmax(fabs(ulo), fabs(uhi)) + fmax(fabs(vlo), fabs(vhi)) + 1.0;
-            const double m = 1e-6 * s * s;
-            if (uhi + m < xlo / fd || ulo - m > xhi / fd || vhi + m < ylo / fd || vlo - m > yhi / fd) continue;
-        }
-        const V3 c = mk(0.5 * (bb[0] + bb[1]), 0.5 * (bb[2] + bb[3]), 0.5 * (bb[4] + bb[5]));
-        const V3 e = mk(bb[1] - bb[0], bb[3] - bb[2], bb[5] - bb[4]);
-        clear = sphere_clear(c, 0.5 * sqrt(dot(e, e)) * (1.0 + 1e-9) + 1e-12);
-    }
-    mask[b] = clear ? 1 : 0;
-}
-
-// The live blocks of a cull mask (one workgroup: each thread counts a contiguous run of the index
-// space, an LDS scan gives the runs' offsets, then each thread writes its run's live blocks).  The
-// index space is the blocks in row-major order, or (morton) the Z-order curve over the tile's
-// blocks padded to a power-of-two square: with block-major work items (RenderArgs::item_order) the
-// waves in flight then cover a compact square of the image instead of a strip.
-__device__ __forceinline__ uint32_t vr_compact1by1(uint32_t x) {
-    x &= 0x55555555u;
-    x = (x | (x >> 1)) & 0x33333333u;
-    x = (x | (x >> 2)) & 0x0F0F0F0Fu;
-    x = (x | (x >> 4)) & 0x00FF00FFu;
-    x = (x | (x >> 8)) & 0x0000FFFFu;
-    return x;
-}
-__global__ __launch_bounds__(1024) void block_compact_kernel(const uint8_t* mask, uint32_t bw, uint32_t bh,
-                                                              uint32_t side, uint32_t* live, uint32_t* count) {
-    __shared__ uint32_t part[1024];
-    const uint32_t n = side ? side * side : bw * bh;  // the index space
-    auto block_of = [&](uint32_t i) -> int64_t {    // the live block at index i, or -1
-        uint32_t b = i;
-        if (side) {
-            const uint32_t x = vr_compact1by1(i), y = vr_compact1by1(i >> 1);
-            if (x >= bw || y >= bh) return -1;
-            b = y * bw + x;
-        }
-        return mask[b] == 0 ? (int64_t)b : -1;
-    };
-    const uint32_t tid = threadIdx.x, per = (n + 1023) / 1024;
-    const uint32_t lo = min(n, tid * per), hi = min(n, lo + per);
-    uint32_t c = 0;
-    for (uint32_t i = lo; i < hi; ++i) c += block_of(i) >= 0;
-    part[tid] = c;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {  // inclusive Hillis-Steele scan
-        const uint32_t v = tid >= d ? part[tid - d] : 0u;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    uint32_t off = part[tid] - c;
-    for (uint32_t i = lo; i < hi; ++i) {
-        const int64_t b = block_of(i);
-        if (b >= 0) live[off++] = (uint32_t)b;
-    }
-    if (tid == 1023) *count = part[1023];
-}
-
-#ifndef VR_REDUCE_BATCH  // samples whose colours the ordered reduce computes together
-#define VR_REDUCE_BATCH 4
-#endif
-typedef double d2 __attribute__((ext_vector_type(2)));
-// accumulation_buffer.rs:44-60 (update_pixel with weight 1.0), one thread per pixel, samples in
-// order: the same Kahan sequence the reference applies call by call.  ANY_WL: the photons are a
-// caller's and their wavelengths any doubles (xyz_for_wavelength_tab); false for the render's own.
-__constant__ double c_exp_tab[64] = VR_EXP_TABLE_INIT;
-template <bool ANY_WL>
-__global__ __launch_bounds__(256) void accumulate_kernel(double* state, const double* staging, uint64_t npix,
-                                                         uint32_t spp, uint32_t accumulate, const uint8_t* mask,
-                                                         uint64_t tile_width, const uint32_t* stage_tag,
-                                                         uint32_t stage_gen, int32_t* error_flag) {
-    // Debug builds (-DVR_STAGE_GUARD): every staged photon the reduce reads must carry this pass's
-    // generation -- a slot the render kernel did not write in this pass is a device error (error
-    // word bit 3, VR_ERROR_DEVICE "staging guard").  The invariant it checks: the reduce reads
-    // slot (s, p) exactly for the pixels p < npix outside culled blocks and the samples s < spp,
-    // and the render kernel's item space covers exactly those (pixel, sample) pairs.
-#ifdef VR_STAGE_GUARD
-    auto guard = [&](uint32_t s, uint64_t p) {
-        if (stage_tag[(uint64_t)s * npix + p] != stage_gen) {
-            if (atomicOr(error_flag, 8) == 0)
-                printf("vr staging guard: pixel %llu sample %u tag %u, pass generation %u\n", (unsigned long long)p, s,
-                       stage_tag[(uint64_t)s * npix + p], stage_gen);
-            atomicOr(error_flag, 8);
-        }
-    };
-#define VR_GUARD(s, p) guard(s, p)
-#else
-#define VR_GUARD(s, p) ((void)stage_tag, (void)stage_gen, (void)error_flag)
-#endif
-    __shared__ double etab[64];  // 2^(j/64) for the lobes' exp (vr_exp_table.h)
-    if (threadIdx.x < 64) etab[threadIdx.x] = c_exp_tab[threadIdx.x];
-    __syncthreads();
-    const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= npix) return;
-    // records (vr_layout.h): the pixel's sums {X, Y, Z, weight} at state[4p], its Kahan
-    // compensations at state[4 npix + 4p] -- 32 B each, one dwordx4 pair per half
-    d2* const rs = reinterpret_cast<d2*>(state + 4 * p);
-    d2* const rb = reinterpret_cast<d2*>(state + 4 * npix + 4 * p);
-    double sum[3] = {0.0, 0.0, 0.0}, bias[3] = {0.0, 0.0, 0.0}, w = 0.0, wb = 0.0;
-    if (accumulate) {
-        const d2 s0 = rs[0], s1 = rs[1], b0 = rb[0], b1 = rb[1];
-        sum[0] = s0.x; sum[1] = s0.y; sum[2] = s1.x; w = s1.y;
-        bias[0] = b0.x; bias[1] = b0.y; bias[2] = b1.x; wb = b1.y;
-    }
-    // update_pixel for one sample (the Kahan chain is sequential in s)
-    auto update = [&](const double c[3]) {
-        const double wy = 1.0 - wb;
-        const double wt = w + wy;
-        wb = (wt - w) - wy;
-        w = wt;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const double y = c[k] * 1.0 - bias[k];
-            const double t = sum[k] + y;
-            bias[k] = (t - sum[k]) - y;
-            sum[k] = t;
-        }
-    };
-    // the colours of kB samples are independent (7 exp() each): computed together, then folded in
-    // order -- the same operations as one at a time, with kB-fold instruction-level parallelism
-    constexpr uint32_t kB = VR_REDUCE_BATCH;
-    uint32_t s = 0;
-    if (mask) {
-        const uint64_t py = p / tile_width, px = p - py * tile_width;
-        if (mask[(py >> 3) * ((tile_width + 7) >> 3) + (px >> 3)]) {
-            // a culled block (block_cull_kernel): every sample is the photon {0, 0}, colour +0.
-            // From a fresh record the Kahan chain has a closed form: colour y = +0 * 1 - +0 = +0
-            // keeps sums and compensations +0, and the weight counts 1, 2, .., spp exactly with
-            // compensation (n + 1 - n) - 1 = 0 (spp < 2^32 < 2^53)
-            if (!accumulate) {
-                w = (double)spp;
-                s = spp;
-            }
-            const double z[3] = {0.0, 0.0, 0.0};
-            for (; s < spp; ++s) update(z);
-        }
-    }
-    for (; s + kB <= spp; s += kB) {
-        double c[kB][3];
-        d2 v[kB];
-        uint64_t bits = 0;  // OR of the batch's photon bits: 0 iff all four are {+0, +0}
-#pragma unroll
-        for (uint32_t j = 0; j < kB; ++j) {
-            // final photon {wavelength, intensity}: one 16-B non-temporal load
-            VR_GUARD(s + j, p);
-            v[j] = __builtin_nontemporal_load(reinterpret_cast<const d2*>(staging) + ((uint64_t)(s + j) * npix + p));
-            bits |= (uint64_t)__double_as_longlong(v[j].x) | (uint64_t)__double_as_longlong(v[j].y);
-        }
-        // the lanes with some nonzero photon bit, as one 64-bit compare into a lane mask.  (Not a
-        // compare of a zero-extended bool "dark" with 0: hipcc of ROCm 7.2 folded that into the
-        // mask of the dark lanes -- the opposite polarity -- once this loop was split in two, so a
-        // wave with ANY dark lane zeroed every lane's colours; DESIGN.md section 8, "the staging
-        // invariant")
-        if (__builtin_amdgcn_uicmpl(bits, 0ull, 33 /* ne */) == 0) {
-            // a missed camera ray's photon {+0, +0} (camera.rs:110-113): every lobe is positive at
-            // 0 nm, so its colour is (+0, +0, +0) exactly -- the wave skips the 28 exp when all
-            // its photons are such (rows of pixels that see no geometry)
-#pragma unroll
-            for (uint32_t j = 0; j < kB; ++j) c[j][0] = c[j][1] = c[j][2] = 0.0;
-        } else {
-#pragma unroll
-            for (uint32_t j = 0; j < kB; ++j) {
-                const double wl = v[j].x, I = v[j].y;
-                const double Is = I * 360.0;                     // photon.rs:26-28, camera.rs:121-126
-                const V3 cx = xyz_for_wavelength_tab<ANY_WL>(wl, etab);  // colour_xyz.rs:31-35
-                c[j][0] = cx.x * Is;
-                c[j][1] = cx.y * Is;
-                c[j][2] = cx.z * Is;
-            }
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < kB; ++j) update(c[j]);
-    }
-    for (; s < spp; ++s) {
-        VR_GUARD(s, p);
-        const d2 v = __builtin_nontemporal_load(reinterpret_cast<const d2*>(staging) + ((uint64_t)s * npix + p));
-        const double wl = v.x, I = v.y;
-        const double Is = I * 360.0;
-        const V3 cx = xyz_for_wavelength_tab<ANY_WL>(wl, etab);
-        const double c[3] = {cx.x * Is, cx.y * Is, cx.z * Is};
-        update(c);
-    }
-    rs[0] = d2{sum[0], sum[1]};
-    rs[1] = d2{sum[2], w};
-    rb[0] = d2{bias[0], bias[1]};
-    rb[1] = d2{bias[2], wb};
-}
-#undef VR_GUARD
-
-template <int STACK>
-__global__ __launch_bounds__(256) void trace_kernel(TraceArgs A) {
-    __shared__ int st_node[STACK * 256];
-    __shared__ float st_t[STACK * 256];
-    const int tid = threadIdx.x;
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + tid;
-    if (i >= A.n) return;
-    Ray r;
-    r.o = ldv(A.origins + 3 * i);
-    r.d = ldv(A.directions + 3 * i);
-    RayPre pre = prepare(r);
-    Counts cnt = {0, 0, 0, 0, 0, 0, 0, 0};
-    Best best = closest_hit<STACK, false>(A.scene, pre, st_node, st_t, tid, cnt);
-    vr_hit_record* out = (vr_hit_record*)A.out + i;
-    out->valid = best.kind != kNone;
-    if (!best.kind) return;
-    HitInfo h;
-    hit_info(A.scene, best, pre, h);
-    out->object = best.object;
-    out->primitive = best.kind == kPrim ? A.scene.prims[best.index].position : best.index;
-    if (best.kind == kTri) {
-        for (int b = 0; b < A.scene.bvh_count; ++b)
-            if (A.scene.bvhs[b].object == best.object)
-                out->primitive = A.scene.tris[best.index].rank - A.scene.bvhs[b].tri_base;  // reference leaf position
-    }
-    out->distance = best.d;
-    out->location[0] = h.loc.x; out->location[1] = h.loc.y; out->location[2] = h.loc.z;
-    out->normal[0] = h.normal.x; out->normal[1] = h.normal.y; out->normal[2] = h.normal.z;
-    out->tangent[0] = h.tangent.x; out->tangent[1] = h.tangent.y; out->tangent[2] = h.tangent.z;
-    out->cotangent[0] = h.cotangent.x; out->cotangent[1] = h.cotangent.y; out->cotangent[2] = h.cotangent.z;
-    out->retro[0] = h.retro.x; out->retro[1] = h.retro.y; out->retro[2] = h.retro.z;
-}
-
 }  // namespace dev
 
 // ----------------------------------------------------------------------------------------------
 // Host-side launch wrappers
 // ----------------------------------------------------------------------------------------------
-static hipError_t launch_reduce(const RenderArgs& a, hipStream_t s, hipEvent_t mid) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (mid) {  // between the render kernel and the ordered reduce (timed launches)
-        e = hipEventRecord(mid, s);
-        if (e != hipSuccess) return e;
-    }
-    const uint64_t npix = a.tile_width * a.tile_height;
-    hipLaunchKernelGGL(dev::accumulate_kernel<false>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, a.state,
-                       (const double*)a.staging, npix, a.spp, a.accumulate, a.block_mask, a.tile_width,
-                       a.stage_tag, a.stage_gen, a.error_flag);
-    return hipGetLastError();
-}
-
-// the ordered reduce on its own, for photons a caller staged (vr_accumulate_photons_device): every
-// pixel's samples are read, there is no cull mask
-int launch_accumulate(double* state, const double* photons, uint64_t npix, uint32_t spp, uint32_t accumulate,
-                      void* stream) {
-#ifdef VR_STAGE_GUARD  // debug builds: caller-staged photons carry no generation tags
-    return (int)hipErrorNotSupported;
-#else
-    if (npix == 0) return 0;
-    hipLaunchKernelGGL(dev::accumulate_kernel<true>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       state, photons, npix, spp, accumulate, (const uint8_t*)nullptr, npix,
-                       (const uint32_t*)nullptr, 0u, (int32_t*)nullptr);
-    return (int)hipGetLastError();
-#endif
-}
-
 // One instantiation of render_kernel, named by field; the defaults are the template's
 struct Variant {
     int stack = 0;
@@ -2036,7 +1652,7 @@ static void launch_variant(Make make, dim3 grid, hipStream_t s, const RenderArgs
 
 template <int STACK, int CAM>
 static hipError_t launch_render_t(const RenderArgs& a, const PoseArgs& pose, const LensArgs& lens, const LaunchChoice& c,
-                                  int grid_limit, hipStream_t s, hipEvent_t mid) {
+                                  int grid_limit, hipStream_t s) {
     // persistent waves: enough workgroups to fill the chip, each wave loops over work items
     const uint64_t items = dev::render_items(a, ((a.tile_width + 7) / 8) * ((a.tile_height + 7) / 8) * 64);
     const uint64_t want = (items + 255) / 256;
@@ -2092,11 +1708,11 @@ static hipError_t launch_render_t(const RenderArgs& a, const PoseArgs& pose, con
         } else {
             VR_MODES(v.big = true);
         }
-        return launch_reduce(a, s, mid);
+        return hipSuccess;
     }
     if (whitted) {
         VR_MODES(v.dark0 = true, v.whitted = true);
-        return launch_reduce(a, s, mid);
+        return hipSuccess;
     }
     // kinds present (bit 0 Lambertian, 1 reflective, 2 Phong or dielectric) -> specialisation:
     // Lambertian-only (1), reflective-only (2) or the general kernel (3)
@@ -2137,70 +1753,17 @@ static hipError_t launch_render_t(const RenderArgs& a, const PoseArgs& pose, con
 #undef VR_TUNING_ARMS
 #undef VR_MODES
 #undef VR_K
-    return launch_reduce(a, s, mid);
+    return hipSuccess;
 }
 
-int launch_block_cull(const RenderArgs& a, const PoseArgs& pose, const LensArgs& lens, uint8_t* mask, void* stream) {
-    const uint64_t blocks = ((a.tile_width + 7) / 8) * ((a.tile_height + 7) / 8);
-    if (blocks == 0) return 0;
-    hipLaunchKernelGGL(dev::block_cull_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       a, a.scene.prims, a.scene.bvhs, mask, pose, lens);
-    return (int)hipGetLastError();
-}
-
-int launch_block_compact(const uint8_t* mask, uint32_t bw, uint32_t bh, bool morton, uint32_t* live, uint32_t* count,
-                         void* stream) {
-    // Z-order only for near-square block grids (the padded square at most 4x the blocks)
-    uint32_t side = 0;
-    if (morton) {
-        side = 1;
-        while (side < bw || side < bh) side <<= 1;
-        if ((uint64_t)side * side > 4ull * bw * bh || side > 32768) side = 0;
-    }
-    hipLaunchKernelGGL(dev::block_compact_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, mask, bw, bh, side, live,
-                       count);
-    return (int)hipGetLastError();
-}
-
+// The launcher of one camera mode's kernels: the stack class of the launch.  Only enqueues the render
+// kernel; launch_render (vr_render_launch.hip) follows it with the ordered reduce.
 template <int CAM>
-static hipError_t launch_render_class(int depth, const RenderArgs& a, const PoseArgs& pose, const LensArgs& lens,
-                                      const LaunchChoice& c, int grid_limit, hipStream_t s, hipEvent_t mid) {
-    if (depth <= 24) return launch_render_t<24, CAM>(a, pose, lens, c, grid_limit, s, mid);
-    if (depth <= 32) return launch_render_t<32, CAM>(a, pose, lens, c, grid_limit, s, mid);
-    return launch_render_t<48, CAM>(a, pose, lens, c, grid_limit, s, mid);
-}
-
-int launch_render(const RenderArgs& a, const PoseArgs& pose, const LensArgs& lens, const LaunchChoice& c, int grid_limit,
-                  void* stream, void* mid_event) {
-    hipStream_t s = (hipStream_t)stream;
-    hipEvent_t mid = (hipEvent_t)mid_event;
-    if (a.tile_width == 0 || a.tile_height == 0 || a.spp == 0) return 0;
-    hipError_t e;
-    // the 64-bit-offset kernels exist in the deepest stack class only (a scene that needs them is
-    // far larger than any whose tree fits the smaller classes; more LDS is only fewer waves)
-    const int depth = c.big && c.stack_depth <= 48 ? 48 : c.stack_depth;
-    if (depth > 48) return -1000;
-    // RenderArgs::posed: the instantiations whose camera step applies the scene's pose, or pose and lens
-    if (a.posed == 2) e = launch_render_class<2>(depth, a, pose, lens, c, grid_limit, s, mid);
-    else if (a.posed) e = launch_render_class<1>(depth, a, pose, lens, c, grid_limit, s, mid);
-    else e = launch_render_class<0>(depth, a, pose, lens, c, grid_limit, s, mid);
-    return (int)e;
-}
-
-int launch_trace(const TraceArgs& a, int stack_depth, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (a.n == 0) return 0;
-    dim3 grid((unsigned)((a.n + 255) / 256)), block(256);
-    if (stack_depth <= 24) hipLaunchKernelGGL(dev::trace_kernel<24>, grid, block, 0, s, a);
-    else if (stack_depth <= 32) hipLaunchKernelGGL(dev::trace_kernel<32>, grid, block, 0, s, a);
-    else if (stack_depth <= 48) hipLaunchKernelGGL(dev::trace_kernel<48>, grid, block, 0, s, a);
-    else return -1000;
-    return (int)hipGetLastError();
-}
-
-const char* device_error_string(int code) {
-    if (code == -1000) return "BVH deeper than the largest traversal stack (48)";
-    return hipGetErrorString((hipError_t)code);
+hipError_t launch_render_class(int depth, const RenderArgs& a, const PoseArgs& pose, const LensArgs& lens,
+                               const LaunchChoice& c, int grid_limit, hipStream_t s) {
+    if (depth <= 24) return launch_render_t<24, CAM>(a, pose, lens, c, grid_limit, s);
+    if (depth <= 32) return launch_render_t<32, CAM>(a, pose, lens, c, grid_limit, s);
+    return launch_render_t<48, CAM>(a, pose, lens, c, grid_limit, s);
 }
 
 }  // namespace vr

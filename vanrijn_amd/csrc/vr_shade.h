@@ -1,5 +1,5 @@
 // vr_shade.h -- one level of the integrators at a closest hit, in pieces (gfx950): what
-// render_kernel's `shade` lambda (vr_render.hip) and integrate_kernel (vr_integrate.hip) both do
+// render_kernel's `shade` lambda (vr_render_kernel.h) and integrate_kernel (vr_integrate.hip) both do
 // between a known hit and the bounce ray, once.  Every function takes and returns values and knows
 // nothing of a path's state (flags, T / Acc / T0 / Acc0 / b0, Wa / Wb, the early stop): the two
 // kernels keep that bookkeeping around these calls.  Each expression is the reference's, in its
