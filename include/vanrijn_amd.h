@@ -830,6 +830,78 @@ int vr_accumulate_photons_device(double* state, const vr_photon* photons, uint64
 int vr_camera_rays_device(const vr_scene* scene, const vr_render_params* params, double* origins,
                           double* directions, uint64_t* stream_ids, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Feature buffers: what the camera rays of a pixel's samples meet first -- normal, depth, coverage,
+ * the object and primitive under the pixel, and the first hit's material colour (albedo) -- for
+ * denoisers, compositing and picking.  Added under ABI 10 (VR_HAS_FEATURES); additions only.
+ *
+ * The rule.  For each pixel of params->tile and each sample first_sample .. first_sample + spp - 1, in
+ *   this order: the sample's camera ray is formed exactly as vr_camera_rays_device and the render form
+ *   it (the scene's pose and lens), its closest hit is found with the rules of vr_query_closest (the
+ *   same walk of the 4-wide tree, scenes on either side of vr_scene_needs_wide_offsets), and the
+ *   sample is folded into the pixel's record with plain f64 additions.  No shading runs and no bounce
+ *   ray is traced.  One GPU lane owns one pixel, so the order of every sum is the sample order whatever
+ *   the tile, the tiling or the split of the samples over calls: spp = 2 followed by spp = 1,
+ *   first_sample = 2, accumulate = 1 gives the bits of spp = 3.
+ * The draws.  The jitter is draws 0 and 1 of stream (seed, row * width + column, sample), x first; in a
+ *   scene with a lens draws 2 and 3 are the lens draws.  Only when the albedo is asked for, a sample that
+ *   hits draws its wavelength next (draw 2, or 4 with a lens): the draw the render takes for it.
+ * The record, 64 B per pixel, row-major in the tile (vr_pixel_features below):
+ *   normal_sum / distance_sum: IntersectionInfo::normal and ::distance summed over the samples that hit.
+ *     NaN normals reach the sums as they reach the pixel in a render (the zero normals mesh.rs:37 gives
+ *     an OBJ without normals are the usual source).  Mean normal = normal_sum * (1 / hits), mean
+ *     depth = distance_sum * (1 / hits), coverage = hits / samples.
+ *   distance_min, object, primitive: of the nearest sample -- the first sample that hit, replaced by a
+ *     later one only if its distance is strictly less (the reference's min_by rule: a NaN distance
+ *     never replaces a hit and is never replaced).  0, -1, -1 while hits == 0.
+ * The albedo (albedo_state, optional): a state array of exactly vr_render_tile_device's layout, 8 doubles
+ *   per pixel, holding update_pixel (weight 1) of one photon per sample in sample order: {0, 0} for a
+ *   miss (camera.rs:110-113); for a hit {lambda, a} with lambda = Photon::random_wavelength from the draw
+ *   above and a = Spectrum::intensity_at_wavelength(lambda) of the hit's material colour (exact; the
+ *   strength factors are not applied; a triangle's own material, vr_scene_set_mesh_materials, is
+ *   honoured), or 1.0 for a dielectric, whose spectrum is an index of refraction.  The x360 pdf scale
+ *   and the CIE conversion are update_pixel's: the array equals vr_accumulate_photons_device of those
+ *   photons bit for bit, so vr_tone_map_device, vr_resolve_state and vr_film_merge_state take it as it
+ *   is.  It converges to the scene's reflectance under flat white light; at low spp it carries the same
+ *   wavelength noise as the beauty image.
+ * accumulate == 1 continues from the records already in both arrays (sums, counts, the nearest sample,
+ *   the Kahan state); 0 starts fresh.
+ * Errors, all before the first device call: a null scene or params, both outputs NULL, or accumulate
+ *   not 0 or 1: VR_ERROR_INVALID_ARGUMENT; a VR_SCENE_HOST_ONLY scene: VR_ERROR_HOST_ONLY; then params
+ *   as vr_render_tile_device checks them (a tile outside the image: VR_ERROR_INVALID_ARGUMENT; an image
+ *   of more than 2^32 pixels or first_sample + spp > 2^32: VR_ERROR_UNSUPPORTED); a tree deeper than
+ *   the largest traversal stack (48): VR_ERROR_UNSUPPORTED.  An empty tile or spp == 0 returns VR_OK
+ *   and touches nothing, as a render.  There is no singular-basis error (nothing is shaded), and
+ *   vr_debug_set_fault_object and vr_debug_set_launch_flags are ignored.
+ * Either output may be NULL; with albedo_state == NULL no wavelength is drawn and no material is read.
+ *   Records are written for the tile's pixels only.  Both arrays must be 16-byte aligned (any hipMalloc
+ *   or torch allocation is).
+ * Limits.  Parallelism is one lane per pixel: a tiny tile at a very large spp runs on few lanes
+ *   (splitting a pixel's samples over lanes would change the order of the sums).  The block cull of the
+ *   render is not used: a ray that misses everything costs its root tests.
+ * --------------------------------------------------------------------------------------------- */
+#define VR_HAS_FEATURES 1
+
+typedef struct vr_pixel_features { /* 64 B, four 16-B quads */
+    double normal_sum[3];  /* sum of IntersectionInfo::normal over the hit samples, in sample order */
+    double distance_sum;   /* sum of IntersectionInfo::distance over the hit samples, in sample order */
+    double distance_min;   /* distance of the nearest hit sample; 0 while hits == 0 */
+    uint32_t hits;         /* samples whose camera ray hit */
+    uint32_t samples;      /* samples folded in */
+    int32_t object;        /* scene object of the nearest sample; -1 while hits == 0 */
+    int32_t reserved;      /* 0 */
+    int64_t primitive;     /* as vr_ray_hit::primitive of the nearest sample; -1 while hits == 0 */
+} vr_pixel_features;
+
+/* features: NULL or device [tile pixels]; albedo_state: NULL or device, 8 doubles per tile pixel.  Only
+ * enqueues on `stream` (NULL = the null stream) of the scene's device; no host synchronisation. */
+int vr_render_features_device(const vr_scene* scene, const vr_render_params* params, vr_pixel_features* features,
+                              double* albedo_state, void* stream);
+/* Host-array form: staged through a call context as vr_query_closest (with accumulate == 1 the arrays are
+ * uploaded first).  Thread-safe, re-entrant, returns when done. */
+int vr_render_features(const vr_scene* scene, const vr_render_params* params, vr_pixel_features* features,
+                       double* albedo_state);
+
 /* Host helpers (scene setup; no device work). */
 /* Spectrum::reflection_from_linear_rgb (spectrum.rs:81-165): 32 samples over [380, 720] nm. */
 int vr_spectrum_reflection_from_linear_rgb(double red, double green, double blue, double out[32]);

@@ -1,5 +1,5 @@
 """VGPR / SGPR / scratch / LDS of the render-kernel instantiations (analysis aid), or of the
-ray-query / integrate kernels' when given vr_query.hip / vr_integrate.hip.  A render kernel is named by its
+ray-query / integrate / feature kernels' when given vr_query.hip / vr_integrate.hip / vr_features.hip.  A render kernel is named by its
 template arguments by name (tools/isa_sections.py kernel_args), whichever revision the source is.
     python tools/kernel_resources.py [--asm FILE] [other/vr_render.hip | vanrijn_amd/csrc/vr_query.hip] [extra hipcc flags]
 With no source: every unit that holds a kernel of the render launch (tools/isa_sections.py device_assembly),
@@ -31,12 +31,12 @@ def report(asm):
 
 def report_kernel(blk):
     name = re.search(r"\.name:\s+(\S+)", blk)
-    args = name and re.search(r"(?:render|query|integrate)_kernelIL(.*?)EEEv", name.group(1))
+    args = name and re.search(r"(?:render|query|integrate|features)_kernelIL(.*?)EEEv", name.group(1))
     if not args:
         return
     render = kernel_args(name.group(1))
     args = kernel_label(render)[len("render_kernel"):] if render else (
-        ("query " if "query_kernel" in name.group(1) else "integrate ") + args.group(1))
+        re.search(r"(query|integrate|features)_kernel", name.group(1)).group(1) + " " + args.group(1))
     f = {k: re.search(r"\." + k + r":\s+(\d+)", blk) for k in
          ("vgpr_count", "sgpr_count", "sgpr_spill_count", "vgpr_spill_count", "private_segment_fixed_size",
           "group_segment_fixed_size")}

@@ -172,6 +172,12 @@ class IntegrateParams(C.Structure):
                 ("first_draw", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class PixelFeatures(C.Structure):
+    _fields_ = [("normal_sum", C.c_double * 3), ("distance_sum", C.c_double), ("distance_min", C.c_double),
+                ("hits", C.c_uint32), ("samples", C.c_uint32), ("object", C.c_int32), ("reserved", C.c_int32),
+                ("primitive", C.c_int64)]
+
+
 # every function declared in include/vanrijn_amd.h: name -> (restype, argtypes)
 _p, _u32, _u64, _i32, _d = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32, C.c_double
 SIGNATURES = {
@@ -222,6 +228,8 @@ SIGNATURES = {
     "vr_integrate_rays": (C.c_int, [_p, _u64, _p, _p, _p, _p, C.POINTER(IntegrateParams), _p, _p]),
     "vr_accumulate_photons_device": (C.c_int, [_p, _p, _u64, _u32, _u32, _i32, _p]),
     "vr_camera_rays_device": (C.c_int, [_p, C.POINTER(RenderParams), _p, _p, _p, _p]),
+    "vr_render_features_device": (C.c_int, [_p, C.POINTER(RenderParams), _p, _p, _p]),
+    "vr_render_features": (C.c_int, [_p, C.POINTER(RenderParams), _p, _p]),
     "vr_spectrum_reflection_from_linear_rgb": (C.c_int, [_d, _d, _d, _p]),
     "vr_spectrum_intensity_at_wavelength": (_d, [C.POINTER(Spectrum), _d]),
     "vr_colour_xyz_for_wavelength": (None, [_d, _p]),

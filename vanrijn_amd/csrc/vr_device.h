@@ -345,6 +345,39 @@ __device__ __forceinline__ V3 xyz_for_wavelength_tab(double wl, const double* ta
               VR_GT(1.217, 437.0, 11.8, 36.0) + VR_GT(0.681, 459.0, 26.0, 13.8));
 }
 #undef VR_GT
+// One pixel's record (RenderArgs::state: sums {X, Y, Z, weight} and their Kahan compensations) held in
+// registers, and update_pixel (accumulation_buffer.rs:44-60) with weight 1.0 of one photon's colour
+// into it: the operations of the ordered reduce's fold (vr_reduce.hip accumulate_kernel), for kernels
+// that fold their own photons (vr_features.hip).  A fresh record is all +0.
+struct PixelSums {
+    double sum[3], bias[3], w, wb;
+    __device__ __forceinline__ void clear() {
+        sum[0] = sum[1] = sum[2] = bias[0] = bias[1] = bias[2] = w = wb = 0.0;
+    }
+    __device__ __forceinline__ void update(const double c[3]) {
+        const double wy = 1.0 - wb;
+        const double wt = w + wy;
+        wb = (wt - w) - wy;
+        w = wt;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double y = c[k] * 1.0 - bias[k];
+            const double t = sum[k] + y;
+            bias[k] = (t - sum[k]) - y;
+            sum[k] = t;
+        }
+    }
+};
+// the colour update_pixel receives for the photon {wl, I}: ColourXyz::from_photon of the photon scaled by
+// the x360 pdf (photon.rs:26-28, camera.rs:121-126, colour_xyz.rs:31-35), as the ordered reduce forms it
+template <bool ANY_WL>
+__device__ __forceinline__ void photon_colour(double wl, double I, const double* tab, double c[3]) {
+    const double Is = I * 360.0;
+    const V3 cx = xyz_for_wavelength_tab<ANY_WL>(wl, tab);
+    c[0] = cx.x * Is;
+    c[1] = cx.y * Is;
+    c[2] = cx.z * Is;
+}
 __device__ __forceinline__ V3 xyz_for_wavelength(double wl) {
     return mk(gaussian(wl, 1.056, 599.8, 37.9, 31.0) + gaussian(wl, 0.362, 442.0, 16.0, 26.7) +
                   gaussian(wl, -0.065, 501.1, 20.4, 26.2),

@@ -1,5 +1,6 @@
 // vr_host_rays.cpp -- the entry points for caller-supplied rays: vr_trace_rays, the ray queries
-// (vr_query.hip), the integrators (vr_integrate.hip), camera rays and photon accumulation.
+// (vr_query.hip), the integrators (vr_integrate.hip), camera rays, photon accumulation and the first-hit
+// feature buffers (vr_features.hip).
 #include "vr_host.h"
 
 using namespace vrh;
@@ -274,6 +275,92 @@ int vr_camera_rays_device(const vr_scene* s, const vr_render_params* p, double* 
     a.stream_ids = stream_ids;
     const int lr = vr::launch_camera_rays(a, stream);
     if (lr) return fail(VR_ERROR_DEVICE, vr::device_error_string(lr));
+    return VR_OK;
+}
+
+// ---- feature buffers (vr_features.hip) ----
+namespace {
+
+// the checks both feature entry points make before their first device call; *go: there is work to do
+int features_check(const vr_scene* s, const vr_render_params* p, const void* features, const void* albedo, bool* go) {
+    *go = false;
+    if (!s || !p) return fail(VR_ERROR_INVALID_ARGUMENT, "null scene or params");
+    if (!features && !albedo) return fail(VR_ERROR_INVALID_ARGUMENT, "both feature outputs are null");
+    if (p->accumulate > 1) return fail(VR_ERROR_INVALID_ARGUMENT, "accumulate must be 0 or 1");
+    const int rc = check_render_params(s, p);  // host-only, the tile, the 2^32 limits, the stack depth
+    if (rc) return rc;
+    const uint64_t tw = p->tile.end_column - p->tile.start_column, th = p->tile.end_row - p->tile.start_row;
+    if (tw * th == 0 || p->spp == 0) return VR_OK;
+    // one wave per 8x8 block, four per workgroup: the block index is 32-bit
+    if (((tw + 7) / 8) * ((th + 7) / 8) >= (1ull << 31))
+        return fail(VR_ERROR_UNSUPPORTED, "too many pixel blocks in one launch (2^31)");
+    *go = true;
+    return VR_OK;
+}
+
+// enqueue the feature pass on `st` (device pointers)
+int features_enqueue(const vr_scene* s, const vr_render_params* p, void* features, double* albedo, hipStream_t st) {
+    const vr::RenderArgs r = make_args(s, p, nullptr);
+    vr::FeaturesArgs a{};
+    a.scene = s->dev;
+    a.pose = s->pose;
+    a.lens = s->lens;
+    a.start_column = r.start_column;
+    a.start_row = r.start_row;
+    a.tile_width = r.tile_width;
+    a.tile_height = r.tile_height;
+    a.width = r.width;
+    a.height = r.height;
+    a.seed_key = r.seed_key;
+    a.first_sample = r.first_sample;
+    a.spp = r.spp;
+    a.accumulate = r.accumulate;
+    a.blocks_per_row = (uint32_t)((r.tile_width + 7) / 8);
+    a.block_count = (uint32_t)(((r.tile_width + 7) / 8) * ((r.tile_height + 7) / 8));
+    for (int k = 0; k < 4; ++k) a.film[k] = r.film[k];
+    a.features = features;
+    a.albedo_state = albedo;
+    const int lr = vr::launch_features(a, wide_stack_depth(s), st);
+    if (lr) return launch_status(lr);
+    return VR_OK;
+}
+
+}  // namespace
+
+int vr_render_features_device(const vr_scene* s, const vr_render_params* p, vr_pixel_features* features,
+                              double* albedo_state, void* stream) {
+    bool go;
+    const int rc = features_check(s, p, features, albedo_state, &go);
+    if (rc || !go) return rc;
+    VR_HIP(hipSetDevice(s->device));
+    return features_enqueue(s, p, features, albedo_state, (hipStream_t)stream);
+}
+
+int vr_render_features(const vr_scene* s, const vr_render_params* p, vr_pixel_features* features, double* albedo_state) {
+    bool go;
+    int rc = features_check(s, p, features, albedo_state, &go);
+    if (rc || !go) return rc;
+    HostCall call;
+    rc = call.begin(s);
+    if (rc) return rc;
+    const hipStream_t st = call.st;
+    const uint64_t npix = (p->tile.end_column - p->tile.start_column) * (p->tile.end_row - p->tile.start_row);
+    const size_t f_bytes = features ? npix * sizeof(vr_pixel_features) : 0, a_bytes = albedo_state ? npix * 64 : 0;
+    const size_t o_f = call.part(f_bytes), o_a = call.part(a_bytes);
+    rc = call.grow();
+    if (rc) return rc;
+    char* const d_f = features ? call.at(o_f) : nullptr;
+    char* const d_a = albedo_state ? call.at(o_a) : nullptr;
+    if (p->accumulate) {  // continue from the caller's records
+        if (features) VR_HIP(hipMemcpyAsync(d_f, features, f_bytes, hipMemcpyHostToDevice, st));
+        if (albedo_state) VR_HIP(hipMemcpyAsync(d_a, albedo_state, a_bytes, hipMemcpyHostToDevice, st));
+    }
+    rc = features_enqueue(s, p, d_f, (double*)d_a, st);
+    if (rc) return rc;
+    if (features) VR_HIP(hipMemcpyAsync(features, d_f, f_bytes, hipMemcpyDeviceToHost, st));
+    if (albedo_state) VR_HIP(hipMemcpyAsync(albedo_state, d_a, a_bytes, hipMemcpyDeviceToHost, st));
+    VR_HIP(hipEventRecord(call.c->done, st));
+    VR_HIP(hipStreamSynchronize(st));
     return VR_OK;
 }
 

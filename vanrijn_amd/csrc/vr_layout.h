@@ -296,6 +296,24 @@ struct CameraRaysArgs {
     uint64_t* stream_ids;        // [spp][tile pixels]
 };
 
+// vr_features.hip: the first-hit feature pass over a tile (device pointers).  The tile, image, seed and
+// sample range are vr_render_params'; pose and lens are the scene's
+struct FeaturesArgs {
+    DeviceScene scene;
+    PoseArgs pose;
+    LensArgs lens;               // lens_radius != 0: the lens rule and draws 2 and 3 (lu, lv)
+    uint64_t start_column, start_row, tile_width, tile_height;
+    uint64_t width, height;
+    uint64_t seed_key, first_sample;
+    uint32_t spp;
+    uint32_t accumulate;         // 1: continue from the records in both arrays
+    uint32_t blocks_per_row;     // 8x8 pixel blocks across the tile
+    uint32_t block_count;        // ... and in the whole tile: one wave each
+    double film[4];              // as RenderArgs::film
+    void* features;              // vr_pixel_features[tile pixels] or nullptr
+    double* albedo_state;        // RenderArgs::state's layout, or nullptr
+};
+
 // counters[] slots of the counting kernel variant
 enum Counter : int {
     kCntBoxTests = 0,
@@ -377,6 +395,10 @@ int launch_query(const QueryArgs& args, int stack_depth, int grid_limit, void* s
 // -1000: deeper than the largest stack class
 int launch_integrate(const IntegrateArgs& args, int stack_depth, int grid_limit, void* stream);
 int launch_camera_rays(const CameraRaysArgs& args, void* stream);
+// vr_features.hip: per-pixel first-hit records (and the albedo state) of args.spp samples of every pixel
+// of the tile, one lane per pixel; stack_depth: the 4-wide tree's LDS stack entries.  Only enqueues.
+// -1000: deeper than the largest stack class
+int launch_features(const FeaturesArgs& args, int stack_depth, void* stream);
 // vr_reduce.hip: the ordered reduce alone -- update_pixel of photons[s * npix + p], s < spp, into the
 // records at `state` (RenderArgs::state's layout), no cull mask
 int launch_accumulate(double* state, const double* photons, uint64_t npix, uint32_t spp, uint32_t accumulate,

@@ -15,6 +15,12 @@ import numpy as np
 RECORD = 8  # f64 per pixel
 SUMS = 4    # f64 per pixel in the merge-exact half
 
+# vr_pixel_features (include/vanrijn_amd.h "Feature buffers"): one 64-B first-hit record per pixel
+PIXEL_FEATURES_DTYPE = np.dtype([("normal_sum", "<f8", (3,)), ("distance_sum", "<f8"), ("distance_min", "<f8"),
+                                 ("hits", "<u4"), ("samples", "<u4"), ("object", "<i4"), ("reserved", "<i4"),
+                                 ("primitive", "<i8")])
+assert PIXEL_FEATURES_DTYPE.itemsize == 64
+
 
 def pixels(state):
     n = state.numel() if hasattr(state, "numel") else state.size

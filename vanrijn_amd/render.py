@@ -374,6 +374,76 @@ def camera_rays_device(scene, tile: Tile, height, width, spp, seed, first_sample
                                           C.c_void_p(stream_ids_ptr), C.c_void_p(stream_ptr or 0)))
 
 
+class FeatureBuffers:
+    """First-hit feature buffers of a tile (vr_render_features): `records`, a [tile height][tile width]
+    array of records.PIXEL_FEATURES_DTYPE, and `albedo_state`, flat state records of render_tile_device's
+    layout (8 f64 per pixel; resolve_state, AccumulationBuffer.from_state and tone mapping take it as it
+    is), or None where the albedo was not asked for."""
+
+    def __init__(self, records, albedo_state=None):
+        self.records = records
+        self.albedo_state = albedo_state
+
+    def _inverse_hits(self):
+        with np.errstate(divide="ignore"):
+            return 1.0 / self.records["hits"].astype(np.float64)
+
+    def normal(self):
+        """Mean shading normal [.., 3]: normal_sum * (1 / hits), 0 where no sample hit (not normalised)."""
+        with np.errstate(invalid="ignore"):
+            mean = self.records["normal_sum"] * self._inverse_hits()[..., None]
+        return np.where(self.records["hits"][..., None] != 0, mean, 0.0)
+
+    def depth(self):
+        """Mean first-hit distance: distance_sum * (1 / hits); NaN (0 * inf) where no sample hit: there is
+        no depth there, and alpha() says so."""
+        with np.errstate(invalid="ignore"):
+            return self.records["distance_sum"] * self._inverse_hits()
+
+    def alpha(self):
+        """Coverage: hits / samples (NaN where no sample was folded in)."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self.records["hits"].astype(np.float64) / self.records["samples"].astype(np.float64)
+
+
+def render_features(scene, tile: Tile, height, width, spp, seed, first_sample=0, albedo=True,
+                    accumulate: FeatureBuffers = None, device=0) -> FeatureBuffers:
+    """First-hit features of spp samples per pixel of `tile` (vr_render_features): per pixel the summed
+    normals and distances, the hit count and the nearest sample's object and primitive, and with `albedo`
+    a state array of the first hits' material colours.  `accumulate`: a FeatureBuffers of the same tile to
+    continue in place (its albedo_state decides whether the albedo is continued)."""
+    ds = _scene_handle(scene, device)
+    n = tile.width() * tile.height()
+    if accumulate is not None:
+        out = accumulate
+        if out.records.shape != (tile.height(), tile.width()) or out.records.dtype != R.PIXEL_FEATURES_DTYPE or \
+                not out.records.flags.c_contiguous:
+            raise ValueError("accumulate: records of another tile")
+        if out.albedo_state is not None and (out.albedo_state.size != R.RECORD * n or
+                                             out.albedo_state.dtype != np.float64 or
+                                             not out.albedo_state.flags.c_contiguous):
+            raise ValueError("accumulate: albedo state of another tile")
+    else:
+        out = FeatureBuffers(np.zeros((tile.height(), tile.width()), dtype=R.PIXEL_FEATURES_DTYPE),
+                             np.zeros(R.RECORD * n) if albedo else None)
+    p = _params(tile, height, width, spp, seed, first_sample, accumulate is not None)
+    N.check(N.lib().vr_render_features(ds.handle, C.byref(p), out.records.ctypes.data_as(C.c_void_p),
+                                       out.albedo_state.ctypes.data_as(C.c_void_p)
+                                       if out.albedo_state is not None else None))
+    return out
+
+
+def render_features_device(scene, tile: Tile, height, width, spp, seed, first_sample, features_ptr, albedo_state_ptr,
+                           stream_ptr=None, accumulate=False, device=0):
+    """Enqueue the feature pass into device memory on a stream, no synchronisation
+    (vr_render_features_device): vr_pixel_features records at `features_ptr` and / or state records at
+    `albedo_state_ptr` (either may be None, not both)."""
+    ds = _scene_handle(scene, device)
+    p = _params(tile, height, width, spp, seed, first_sample, accumulate)
+    N.check(N.lib().vr_render_features_device(ds.handle, C.byref(p), C.c_void_p(features_ptr or 0),
+                                              C.c_void_p(albedo_state_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+
 def render_tile_device(scene, tile: Tile, height, width, spp, seed, first_sample, state_ptr, stream_ptr=None,
                        accumulate=False, timed=False, counters=False, device=0, defer_times=False, cull=True,
                        dist_cull=True, coop=True, lone_walk=True, stack16=True, one_bvh=True):
