@@ -902,6 +902,105 @@ int vr_render_features_device(const vr_scene* scene, const vr_render_params* par
 int vr_render_features(const vr_scene* scene, const vr_render_params* params, vr_pixel_features* features,
                        double* albedo_state);
 
+/* ---------------------------------------------------------------------------------------------
+ * Denoiser: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010; the spatial filter of SVGF)
+ * over a noisy state array, guided by the feature records and, optionally, the albedo state of
+ * vr_render_features*.  A pure function of its arrays: no scene, no tree, no random stream.  Added
+ * under ABI 10 (VR_HAS_DENOISE); additions only.
+ *
+ * The rule.  All arithmetic is IEEE binary64, in exactly the order written, with no contraction; the
+ *   host form and the device form give the same bits.  n = width * height, pixels row-major.
+ * Inputs per pixel p.
+ *   Presence: w_p = state[4p + 3].  A pixel with w_p == 0 is absent: as a tap it is skipped, as a centre
+ *     it produces the all-zero output record (8 zeros).
+ *   Colour: c_p[k] = state[4p + k] * (1 / w_p), k = 0..2 (only the sums half of the state is read; the
+ *     layout is vr_render_tile_device's).
+ *   Guide: h = features[p].hits.  h == 0: the pixel is background.  Otherwise inv = 1 / (double)h,
+ *     g_p = normal_sum * inv (three products), z_p = distance_sum * inv, iz_p = 1 / z_p,
+ *     o_p = features[p].object.
+ *   Albedo (only with VR_DENOISE_DEMODULATE, which requires albedo_state): a_p[k] is formed from
+ *     albedo_state exactly as c_p from state, and is 0 where the albedo weight is 0.  Channel k of pixel
+ *     p is demodulated when a_p[k] > VR_DENOISE_ALBEDO_FLOOR; then c_p[k] = c_p[k] / a_p[k] before the
+ *     first iteration.
+ * Constants, computed once on the host and passed to the kernels: kc_0 = 1 / (sigma_colour *
+ *   sigma_colour); kc_i = kc_0 * 4^i (an exact scaling: the colour sigma halves per iteration);
+ *   kn = 1 / (sigma_normal * sigma_normal); kz = 1 / (sigma_depth * sigma_depth);
+ *   hk[5] = {1/16, 1/4, 3/8, 1/4, 1/16}.
+ * Iteration i = 0 .. iterations - 1, step s = 2^i, reads colours c and writes c'; the guides never
+ *   change.  For centre p = (x, y), visit the taps q = (x + dx*s, y + dy*s) with dy = -2..2 in the outer
+ *   loop and dx = -2..2 in the inner loop; the centre tap is visited in its place.  A tap is skipped if
+ *   q lies outside the image; q is absent; exactly one of p and q is background;
+ *   VR_DENOISE_MATCH_OBJECT is set, both hit, and o_p != o_q; e (below) is NaN; or w (below) is 0.
+ *   For a tap that is not skipped earlier:
+ *     d = c_q - c_p, e_c = ((d0*d0 + d1*d1) + d2*d2) * kc_i.
+ *     If both p and q are background, e_n = e_z = 0.  Otherwise m = g_q - g_p,
+ *     e_n = ((m0*m0 + m1*m1) + m2*m2) * kn, t = (z_q - z_p) * iz_p, e_z = (t * t) * kz.
+ *     e = (e_c + e_n) + e_z.
+ *     w = (hk[dy+2] * hk[dx+2]) * vr_exp_tab(-e)   (the table-driven exp of the ordered reduce, on
+ *     host and device alike).
+ *     S_k = S_k + w * c_q[k] and W = W + w, both starting from +0.0.
+ *   The result is c'_p[k] = S_k * (1 / W).  If the centre tap itself was skipped, c'_p = c_p instead: a
+ *   NaN or infinite colour, NaN normals or a mean depth of 0 make the pixel pass through unchanged, and
+ *   it poisons no neighbour.  An absent centre stays absent.
+ * Output.  Demodulated channels are multiplied back, c[k] * a_p[k].  out_state[4p .. 4p+3] =
+ *   {c0, c1, c2, 1.0} and out_state[4n + 4p .. 4n + 4p+3] = 0, so vr_tone_map_device, vr_resolve_state
+ *   and vr_film_merge_state take the output as it is (X * (1 / 1.0) is X).  Records are written for the
+ *   n pixels only.  out_state may be the same array as state: everything the filter needs is copied
+ *   into the workspace first.
+ * Errors, all before anything is written or enqueued.  VR_ERROR_INVALID_ARGUMENT: a null params, state,
+ *   features or out_state; a null workspace with n > 0 (device form); iterations outside 1..8; an
+ *   unknown flag (or both VR_DENOISE_LOADS_* at once); VR_DENOISE_DEMODULATE without an albedo; a sigma
+ *   that is not finite or is <= 0; a device array that is not 16-byte aligned.  VR_ERROR_UNSUPPORTED:
+ *   more than 2^31 pixels; in the device forms also an image of 2^24 or more blocks of 64 x 4 pixels
+ *   (started blocks count whole: an image one pixel wide and 2^26 high is one).  width * height == 0
+ *   returns VR_OK and touches nothing.
+ * Limits.  No temporal accumulation and no variance estimate (the state carries no second moment): the
+ *   colour weight compares noisy means, so sigma_colour trades noise left against detail lost.
+ *   vr_denoise_host runs on one thread.
+ * --------------------------------------------------------------------------------------------- */
+#define VR_HAS_DENOISE 1
+
+#define VR_DENOISE_MATCH_OBJECT 1u /* a tap of another object (vr_pixel_features::object) is skipped */
+#define VR_DENOISE_DEMODULATE 2u   /* filter colour / albedo, multiply the albedo back at the end */
+/* How an iteration's taps are loaded; the result's bits are the same.  Neither: the library's own choice
+ * per step ("Denoiser").  For measurement and the tests. */
+#define VR_DENOISE_LOADS_DIRECT 4u /* every step reads the workspace directly */
+#define VR_DENOISE_LOADS_LDS 8u    /* every step up to VR_DENOISE_LDS_MAX_STEP stages its tap rows in LDS */
+#define VR_DENOISE_LDS_MAX_STEP 16u
+#define VR_DENOISE_ALBEDO_FLOOR (1.0 / 1024.0)
+#define VR_DENOISE_MAX_ITERATIONS 8u
+
+typedef struct vr_denoise_params {
+    uint64_t width, height;
+    uint32_t iterations; /* 1..8; iteration i has tap spacing 2^i */
+    uint32_t flags;      /* VR_DENOISE_* */
+    double sigma_colour, sigma_normal, sigma_depth; /* of XYZ colour, of the mean normal, of relative depth */
+} vr_denoise_params;
+
+/* iterations 5, no flags, sigma_colour 32 (the least XYZ RMSE of the sweep in DESIGN.md section 2, "Denoiser"),
+ * sigma_normal 0.5, sigma_depth 0.1. */
+int vr_denoise_default_params(uint64_t width, uint64_t height, vr_denoise_params* out);
+/* The device form's workspace: 128 B per pixel (two colour buffers, the guides, the albedo). */
+int vr_denoise_workspace_bytes(const vr_denoise_params* params, uint64_t* out_bytes);
+/* state, features, albedo_state (NULL allowed), out_state and workspace are device pointers, 16-byte
+ * aligned.  Only enqueues on `stream` (NULL = the null stream) of `device`: no host synchronisation and
+ * no allocation. */
+int vr_denoise_device(const vr_denoise_params* params, const double* state, const vr_pixel_features* features,
+                      const double* albedo_state, double* out_state, void* workspace, int32_t device, void* stream);
+/* Measurement hook: enqueues one stage of vr_denoise_device with its checks -- stage 0 the prepare kernel,
+ * 1 .. iterations the iteration stage - 1, iterations + 1 the finish kernel; another stage is
+ * VR_ERROR_INVALID_ARGUMENT.  The stages in order are vr_denoise_device. */
+int vr_denoise_stage_device(const vr_denoise_params* params, uint32_t stage, const double* state,
+                            const vr_pixel_features* features, const double* albedo_state, double* out_state,
+                            void* workspace, int32_t device, void* stream);
+/* Host arrays, staged through the device; returns when done. */
+int vr_denoise(const vr_denoise_params* params, const double* state, const vr_pixel_features* features,
+               const double* albedo_state, double* out_state, int32_t device);
+/* The same rule in plain C++ on host arrays, with no device call at all: the counterpart of the
+ * VR_SCENE_HOST_ONLY paths, for a machine with no GPU. */
+int vr_denoise_host(const vr_denoise_params* params, const double* state, const vr_pixel_features* features,
+                    const double* albedo_state, double* out_state);
+
 /* Host helpers (scene setup; no device work). */
 /* Spectrum::reflection_from_linear_rgb (spectrum.rs:81-165): 32 samples over [380, 720] nm. */
 int vr_spectrum_reflection_from_linear_rgb(double red, double green, double blue, double out[32]);

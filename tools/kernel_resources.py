@@ -1,5 +1,6 @@
 """VGPR / SGPR / scratch / LDS of the render-kernel instantiations (analysis aid), or of the
-ray-query / integrate / feature kernels' when given vr_query.hip / vr_integrate.hip / vr_features.hip.  A render kernel is named by its
+ray-query / integrate / feature / denoise kernels' when given vr_query.hip / vr_integrate.hip / vr_features.hip /
+vr_denoise.hip.  A render kernel is named by its
 template arguments by name (tools/isa_sections.py kernel_args), whichever revision the source is.
     python tools/kernel_resources.py [--asm FILE] [other/vr_render.hip | vanrijn_amd/csrc/vr_query.hip] [extra hipcc flags]
 With no source: every unit that holds a kernel of the render launch (tools/isa_sections.py device_assembly),
@@ -32,10 +33,11 @@ def report(asm):
 def report_kernel(blk):
     name = re.search(r"\.name:\s+(\S+)", blk)
     args = name and re.search(r"(?:render|query|integrate|features)_kernelIL(.*?)EEEv", name.group(1))
-    if not args:
+    plain = name and re.search(r"\d+(denoise_\w+?_kernel)E", name.group(1))  # not a template: its own name
+    if not args and not plain:
         return
-    render = kernel_args(name.group(1))
-    args = kernel_label(render)[len("render_kernel"):] if render else (
+    render = kernel_args(name.group(1)) if args else None
+    args = plain.group(1) if plain else kernel_label(render)[len("render_kernel"):] if render else (
         re.search(r"(query|integrate|features)_kernel", name.group(1)).group(1) + " " + args.group(1))
     f = {k: re.search(r"\." + k + r":\s+(\d+)", blk) for k in
          ("vgpr_count", "sgpr_count", "sgpr_spill_count", "vgpr_spill_count", "private_segment_fixed_size",

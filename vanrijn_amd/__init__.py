@@ -8,7 +8,8 @@ from .render import (AccumulationBuffer, Film, ImageRgbU8, Tile, TileIterator, p
                      render_tile, render_tile_device, resolve_state, tone_map_device, trace_rays, RAY_HIT_DTYPE,
                      query_any, query_any_device, query_closest, query_closest_device, PHOTON_DTYPE,
                      PATH_INFO_DTYPE, integrate_rays, integrate_rays_device, accumulate_photons_device,
-                     camera_rays_device, FeatureBuffers, render_features, render_features_device)
+                     camera_rays_device, FeatureBuffers, render_features, render_features_device, DenoiseParams,
+                     denoise, denoise_device, denoise_workspace_bytes)
 from .scene import (BoundingVolumeHierarchy, ColourRgbF, DeviceScene, DirectionalLight, LambertianMaterial,
                     MaterialSpec, Mesh, PrimitiveSpec, CameraPose, look_at, CameraLens, lens_point,
                     NamedColour, PhongMaterial, Plane, WhittedIntegrator, ReflectiveMaterial, Scene, SceneSpec, SmoothTransparentDialectric, Sphere,
@@ -23,7 +24,8 @@ __all__ = [
     "RAY_HIT_DTYPE", "query_any", "query_any_device", "query_closest", "query_closest_device",
     "PHOTON_DTYPE", "PATH_INFO_DTYPE", "integrate_rays", "integrate_rays_device", "accumulate_photons_device",
     "camera_rays_device", "MaterialSpec", "PrimitiveSpec", "CameraPose", "look_at", "CameraLens", "lens_point",
-    "load_obj_groups", "FeatureBuffers", "render_features", "render_features_device",
+    "load_obj_groups", "FeatureBuffers", "render_features", "render_features_device", "DenoiseParams", "denoise",
+    "denoise_device", "denoise_workspace_bytes",
 ]
 
 

@@ -178,6 +178,15 @@ class PixelFeatures(C.Structure):
                 ("primitive", C.c_int64)]
 
 
+DENOISE_MATCH_OBJECT, DENOISE_DEMODULATE, DENOISE_LOADS_DIRECT, DENOISE_LOADS_LDS = 1, 2, 4, 8
+DENOISE_ALBEDO_FLOOR = 1.0 / 1024.0
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("width", C.c_uint64), ("height", C.c_uint64), ("iterations", C.c_uint32), ("flags", C.c_uint32),
+                ("sigma_colour", C.c_double), ("sigma_normal", C.c_double), ("sigma_depth", C.c_double)]
+
+
 # every function declared in include/vanrijn_amd.h: name -> (restype, argtypes)
 _p, _u32, _u64, _i32, _d = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32, C.c_double
 SIGNATURES = {
@@ -230,6 +239,12 @@ SIGNATURES = {
     "vr_camera_rays_device": (C.c_int, [_p, C.POINTER(RenderParams), _p, _p, _p, _p]),
     "vr_render_features_device": (C.c_int, [_p, C.POINTER(RenderParams), _p, _p, _p]),
     "vr_render_features": (C.c_int, [_p, C.POINTER(RenderParams), _p, _p]),
+    "vr_denoise_default_params": (C.c_int, [_u64, _u64, C.POINTER(DenoiseParams)]),
+    "vr_denoise_workspace_bytes": (C.c_int, [C.POINTER(DenoiseParams), C.POINTER(_u64)]),
+    "vr_denoise_device": (C.c_int, [C.POINTER(DenoiseParams), _p, _p, _p, _p, _p, _i32, _p]),
+    "vr_denoise_stage_device": (C.c_int, [C.POINTER(DenoiseParams), _u32, _p, _p, _p, _p, _p, _i32, _p]),
+    "vr_denoise": (C.c_int, [C.POINTER(DenoiseParams), _p, _p, _p, _p, _i32]),
+    "vr_denoise_host": (C.c_int, [C.POINTER(DenoiseParams), _p, _p, _p, _p]),
     "vr_spectrum_reflection_from_linear_rgb": (C.c_int, [_d, _d, _d, _p]),
     "vr_spectrum_intensity_at_wavelength": (_d, [C.POINTER(Spectrum), _d]),
     "vr_colour_xyz_for_wavelength": (None, [_d, _p]),

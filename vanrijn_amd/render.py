@@ -444,6 +444,82 @@ def render_features_device(scene, tile: Tile, height, width, spp, seed, first_sa
                                               C.c_void_p(albedo_state_ptr or 0), C.c_void_p(stream_ptr or 0)))
 
 
+class DenoiseParams(N.DenoiseParams):
+    """vr_denoise_params (its fields are this object's): the image size, the iterations (1..8, tap spacing
+    2^i), the flags and the three sigmas; the library's defaults where an argument is None.  `loads`: None
+    (the library's choice per step), "direct" or "lds" -- how the device form reads its taps; the bits are
+    the same."""
+
+    def __init__(self, width, height, iterations=None, sigma_colour=None, sigma_normal=None, sigma_depth=None,
+                 match_object=False, demodulate=False, loads=None):
+        super().__init__()
+        N.check(N.lib().vr_denoise_default_params(width, height, C.byref(self)))
+        for name, value in (("iterations", iterations), ("sigma_colour", sigma_colour), ("sigma_normal", sigma_normal),
+                            ("sigma_depth", sigma_depth)):
+            if value is not None:
+                setattr(self, name, value)
+        self.flags = (N.DENOISE_MATCH_OBJECT if match_object else 0) | (N.DENOISE_DEMODULATE if demodulate else 0) | \
+            {None: 0, "direct": N.DENOISE_LOADS_DIRECT, "lds": N.DENOISE_LOADS_LDS}[loads]
+
+    def __repr__(self):
+        return "DenoiseParams(%s)" % ", ".join(f"{n}={getattr(self, n)!r}" for n, _ in self._fields_)
+
+
+def denoise_workspace_bytes(params: DenoiseParams) -> int:
+    """Bytes of device workspace denoise_device needs (vr_denoise_workspace_bytes): 128 per pixel."""
+    out = C.c_uint64()
+    N.check(N.lib().vr_denoise_workspace_bytes(C.byref(params), C.byref(out)))
+    return out.value
+
+
+def denoise(state, features, albedo_state=None, params: DenoiseParams = None, device=0, host=False):
+    """The edge-avoiding a-trous filter of include/vanrijn_amd.h ("Denoiser") on host arrays: `state`, flat
+    state records (8 f64 per pixel); `features`, a FeatureBuffers or a [height][width] array of
+    records.PIXEL_FEATURES_DTYPE; `albedo_state`, state records of the albedo (default: the FeatureBuffers'
+    own, used only when params asks to demodulate).  Returns a new state array that resolve_state, tone
+    mapping and Film.merge_state take as it is.  `params` None: the defaults at the features' shape.
+    `host`: vr_denoise_host, the same rule and bits in plain C++ with no device call; otherwise the arrays
+    are staged through the device (vr_denoise)."""
+    if isinstance(features, FeatureBuffers):
+        if albedo_state is None:
+            albedo_state = features.albedo_state
+        features = features.records
+    rec = np.ascontiguousarray(features, dtype=R.PIXEL_FEATURES_DTYPE)
+    if params is None:
+        if rec.ndim != 2:
+            raise ValueError("denoise: params=None needs [height][width] feature records")
+        params = DenoiseParams(rec.shape[1], rec.shape[0])
+    n = params.width * params.height
+    s = np.ascontiguousarray(np.asarray(state, dtype=np.float64).reshape(-1))
+    if s.size != R.RECORD * n or rec.size != n:
+        raise ValueError("denoise: state or features of another image size")
+    a = None
+    if albedo_state is not None:
+        a = np.ascontiguousarray(np.asarray(albedo_state, dtype=np.float64).reshape(-1))
+        if a.size != R.RECORD * n:
+            raise ValueError("denoise: albedo state of another image size")
+    out = np.zeros(R.RECORD * n)
+    args = (C.byref(params), s.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p),
+            a.ctypes.data_as(C.c_void_p) if a is not None else None, out.ctypes.data_as(C.c_void_p))
+    N.check(N.lib().vr_denoise_host(*args) if host else N.lib().vr_denoise(*args, device))
+    return out
+
+
+def denoise_device(params: DenoiseParams, state_ptr, features_ptr, albedo_ptr, out_ptr, workspace_ptr, stream_ptr=None,
+                   device=0, stage=None):
+    """Enqueue the filter on device arrays on a stream, no synchronisation and no allocation
+    (vr_denoise_device): state records at `state_ptr`, vr_pixel_features at `features_ptr`, the albedo's
+    state records at `albedo_ptr` (or None), the output records at `out_ptr` (may be `state_ptr`) and
+    denoise_workspace_bytes(params) bytes at `workspace_ptr`.  `stage`: only that stage
+    (vr_denoise_stage_device: 0 prepare, 1..iterations an iteration, iterations + 1 finish)."""
+    common = (C.c_void_p(state_ptr or 0), C.c_void_p(features_ptr or 0), C.c_void_p(albedo_ptr or 0),
+              C.c_void_p(out_ptr or 0), C.c_void_p(workspace_ptr or 0), device, C.c_void_p(stream_ptr or 0))
+    if stage is None:
+        N.check(N.lib().vr_denoise_device(C.byref(params), *common))
+    else:
+        N.check(N.lib().vr_denoise_stage_device(C.byref(params), stage, *common))
+
+
 def render_tile_device(scene, tile: Tile, height, width, spp, seed, first_sample, state_ptr, stream_ptr=None,
                        accumulate=False, timed=False, counters=False, device=0, defer_times=False, cull=True,
                        dist_cull=True, coop=True, lone_walk=True, stack16=True, one_bvh=True):
