@@ -954,9 +954,9 @@ int vr_render_features(const vr_scene* scene, const vr_render_params* params, vr
  *   more than 2^31 pixels; in the device forms also an image of 2^24 or more blocks of 64 x 4 pixels
  *   (started blocks count whole: an image one pixel wide and 2^26 high is one).  width * height == 0
  *   returns VR_OK and touches nothing.
- * Limits.  No temporal accumulation and no variance estimate (the state carries no second moment): the
- *   colour weight compares noisy means, so sigma_colour trades noise left against detail lost.
- *   vr_denoise_host runs on one thread.
+ * Limits.  No variance estimate (the state carries no second moment): the colour weight compares noisy
+ *   means, so sigma_colour trades noise left against detail lost.  Temporal accumulation is a stage of
+ *   its own that runs before this one ("Temporal reprojection" below).  vr_denoise_host runs on one thread.
  * --------------------------------------------------------------------------------------------- */
 #define VR_HAS_DENOISE 1
 
@@ -1000,6 +1000,112 @@ int vr_denoise(const vr_denoise_params* params, const double* state, const vr_pi
  * VR_SCENE_HOST_ONLY paths, for a machine with no GPU. */
 int vr_denoise_host(const vr_denoise_params* params, const double* state, const vr_pixel_features* features,
                     const double* albedo_state, double* out_state);
+
+/* ---------------------------------------------------------------------------------------------
+ * Temporal reprojection: carries an accumulated image across a camera move (or a rigid motion of scene
+ * objects).  The previous accumulation is reprojected into the new view through the feature records of
+ * both frames, validated against the geometry, and the new frame's sums are added to it; the result is a
+ * state array again, the denoiser's input.  A pure function of its arrays: no scene, no tree, no random
+ * stream.  Added under ABI 10 (VR_HAS_REPROJECT); additions only.
+ *
+ * Arguments.  state, features: the current frame -- a vr_render_tile_device state and the records of
+ *   vr_render_features* of the same full width x height image.  previous_state: the history -- the
+ *   previous call's out_state, or the previous frame's state at start-up; previous_features: the previous
+ *   frame's records.  Both frames describe the same width x height image.  motion: NULL, or motion_count
+ *   rows of 12 doubles; row o is a row-major 3x4 matrix [A | t] that maps a current-frame world position
+ *   on scene object o (vr_pixel_features::object) to where that point was in the previous frame -- for a
+ *   mesh placed by vr_scene_transform_mesh, M_prev * M_cur^-1.  Objects >= motion_count did not move.  The
+ *   rows are meant for rigid motions: the mean normal goes through A itself, not through its cofactors.
+ *   out_state: a state array; it may be `state` (a pixel reads only its own current record), it may not
+ *   be previous_state, which is gathered.
+ *
+ * The rule.  All arithmetic is IEEE binary64, in exactly the order written, with no contraction; the
+ *   three forms give the same bits.  n = width * height, pixels row-major, p = row * width + column.  The
+ *   lens is ignored: geometry uses the pinhole ray through the pixel centre.  dt2 = depth_tolerance *
+ *   depth_tolerance and nt2 = normal_tolerance * normal_tolerance are formed once on the host.  A step
+ *   that says "no history" leaves the record of step 1 as the output's sums record.
+ *   1. Current record.  W = state[4p+3].  W == 0: the output record is 8 zeros (absent, as in the
+ *      denoiser).  Otherwise the record starts as {state[4p], state[4p+1], state[4p+2], W}.
+ *   2. Geometry.  h = features[p].hits; h == 0: no history.  inv = 1 / (double)h, g = normal_sum * inv
+ *      (three products), z = distance_sum * inv.  Not (z > 0), or z infinite: no history.
+ *      d = the camera ray rule's direction (above, "Camera pose") of `pose` at the film point of the
+ *      pixel centre, jitter (0.5, 0.5).  P_c = location_c + d_c * z for each component c.
+ *   3. Motion.  o = features[p].object.  If motion != NULL and 0 <= o < motion_count, with m = row o:
+ *      P'_c = ((m[4c] * P_x + m[4c+1] * P_y) + m[4c+2] * P_z) + m[4c+3]   (vr_scene_transform_mesh's order)
+ *      g'_c = (m[4c] * g_x + m[4c+1] * g_y) + m[4c+2] * g_z.   Otherwise P' = P and g' = g.
+ *   4. Same-view shortcut.  If pose and previous_pose are equal field by field (== on all 13 doubles) and
+ *      the pixel has no motion row or its row equals the identity entry by entry: the footprint is the
+ *      single tap q = p with b = 1, and z' = z, iz' = 1 / z; go to step 7.  (Progressive accumulation of
+ *      a still view is exact: the output's sums are state + previous_state element by element.)
+ *   5. Projection, on previous_pose.  v = P' - location.  a = (v_x * right_x + v_y * right_y) + v_z *
+ *      right_z; bb with up and c with forward the same way.  Not (c > 0): no history.
+ *      s = film_distance / c, x' = a * s, y' = bb * s.  z' = sqrt((v_x * v_x + v_y * v_y) + v_z * v_z),
+ *      iz' = 1 / z'.  With film[4] the film constants of width x height (film_w / width, film_w / 2,
+ *      film_h / height, film_h / 2 as the ray rule forms them):
+ *      fx = (x' + film[1]) / film[0] - 0.5,  fy = (y' + film[3]) / film[2] - 0.5,
+ *      fr = (double)(height - 1) - fy.
+ *   6. Footprint.  Not (fx >= -1 && fx < (double)width && fr >= -1 && fr < (double)height): no history
+ *      (tested before any conversion to an integer: NaN and overflow end here).  ix = floor(fx),
+ *      tx = fx - ix; iy = floor(fr), ty = fr - iy.  Taps in the order (dy, dx) = (0,0), (0,1), (1,0),
+ *      (1,1) at q = (row iy + dy, column ix + dx) with b = (dx ? tx : 1 - tx) * (dy ? ty : 1 - ty).  A
+ *      tap with b == 0, or outside the image, is skipped unread.
+ *   7. Tap test.  S_q[0..2] = previous_state[4q .. 4q+2], W_q = previous_state[4q+3].  The tap is skipped
+ *      if any of the four is not finite (x - x != 0); W_q == 0; previous_features[q].hits == 0;
+ *      VR_REPROJECT_MATCH_OBJECT is set and previous_features[q].object != o; with invq = 1 /
+ *      (double)hits_q, z_q = distance_sum_q * invq and t = (z_q - z') * iz', not (t * t <= dt2); with
+ *      m = normal_sum_q * invq - g' (three products, three differences), not (((m0 * m0 + m1 * m1) +
+ *      m2 * m2) <= nt2).  A NaN fails either comparison, so a NaN guide poisons nothing.
+ *   8. Fold.  From +0.0, for each tap kept, in tap order: B = B + b, H_k = H_k + b * S_q[k],
+ *      Wh = Wh + b * W_q.  B == 0: no history.  Otherwise r = 1 / B, H_k = H_k * r, Wh = Wh * r (the
+ *      footprint is renormalised over its valid taps).
+ *   9. Cap.  If Wh > max_history_weight: f = max_history_weight / Wh, H_k = H_k * f, Wh =
+ *      max_history_weight.  A finite cap is the usual exponential moving average: the new frame's share
+ *      never falls below W / (cap + W).
+ *   10. Output.  out_state[4p+k] = state[4p+k] + H_k, out_state[4p+3] = W + Wh, and
+ *      out_state[4n+4p .. 4n+4p+3] = 0 (the bias half), so vr_tone_map_device, vr_resolve_state,
+ *      vr_film_merge_state and the denoiser take the output as it is.  Records are written for the n
+ *      pixels only.
+ * Errors, all before anything is written or enqueued.  VR_ERROR_INVALID_ARGUMENT: a null params, state,
+ *   features, previous_state, previous_features or out_state; motion == NULL with motion_count > 0;
+ *   out_state == previous_state; an unknown flag; a tolerance that is not finite or is <= 0;
+ *   max_history_weight NaN or <= 0 (+inf is allowed: no cap); a pose that vr_scene_set_camera_pose would
+ *   refuse; a device array that is not 16-byte aligned.  VR_ERROR_UNSUPPORTED: more than 2^31 pixels; in
+ *   the device forms also an image of 2^24 or more blocks of 64 x 4 pixels, as the denoiser.
+ *   width * height == 0 returns VR_OK and touches nothing.
+ * Limits.  No lens-aware reprojection, no motion-vector output, no variance estimate.  A deforming mesh
+ *   (vr_scene_update_mesh) has no motion row: its history survives only where the validity tests pass.
+ *   vr_reproject_host runs on one thread.
+ * --------------------------------------------------------------------------------------------- */
+#define VR_HAS_REPROJECT 1
+
+#define VR_REPROJECT_MATCH_OBJECT 1u /* a previous-frame tap of another object is skipped */
+
+typedef struct vr_reproject_params { /* 256 B */
+    uint64_t width, height;
+    vr_camera_pose pose, previous_pose; /* of the current frame and of the frame `previous_*` was rendered from */
+    double depth_tolerance;             /* relative, > 0 */
+    double normal_tolerance;            /* of the mean normal's difference, > 0 */
+    double max_history_weight;          /* > 0, +inf allowed: caps the weight the history brings */
+    uint32_t flags, motion_count;       /* VR_REPROJECT_*; rows of `motion` */
+} vr_reproject_params;
+
+/* depth_tolerance 0.05, normal_tolerance 0.25, max_history_weight 64, VR_REPROJECT_MATCH_OBJECT,
+ * motion_count 0 ("Temporal reprojection").  The poses are copied, not validated. */
+int vr_reproject_default_params(uint64_t width, uint64_t height, const vr_camera_pose* pose,
+                                const vr_camera_pose* previous_pose, vr_reproject_params* out);
+/* Every array is a device pointer, 16-byte aligned (motion too, where given).  Only enqueues on `stream`
+ * (NULL = the null stream) of `device`: no host synchronisation, no allocation, no workspace. */
+int vr_reproject_device(const vr_reproject_params* params, const double* state, const vr_pixel_features* features,
+                        const double* previous_state, const vr_pixel_features* previous_features,
+                        const double* motion, double* out_state, int32_t device, void* stream);
+/* Host arrays, staged through the device; returns when done. */
+int vr_reproject(const vr_reproject_params* params, const double* state, const vr_pixel_features* features,
+                 const double* previous_state, const vr_pixel_features* previous_features, const double* motion,
+                 double* out_state, int32_t device);
+/* The same rule in plain C++ on host arrays, with no device call at all. */
+int vr_reproject_host(const vr_reproject_params* params, const double* state, const vr_pixel_features* features,
+                      const double* previous_state, const vr_pixel_features* previous_features,
+                      const double* motion, double* out_state);
 
 /* Host helpers (scene setup; no device work). */
 /* Spectrum::reflection_from_linear_rgb (spectrum.rs:81-165): 32 samples over [380, 720] nm. */

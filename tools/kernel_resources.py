@@ -1,6 +1,6 @@
 """VGPR / SGPR / scratch / LDS of the render-kernel instantiations (analysis aid), or of the
-ray-query / integrate / feature / denoise kernels' when given vr_query.hip / vr_integrate.hip / vr_features.hip /
-vr_denoise.hip.  A render kernel is named by its
+ray-query / integrate / feature / denoise / reprojection kernels' when given vr_query.hip / vr_integrate.hip /
+vr_features.hip / vr_denoise.hip / vr_reproject.hip.  A render kernel is named by its
 template arguments by name (tools/isa_sections.py kernel_args), whichever revision the source is.
     python tools/kernel_resources.py [--asm FILE] [other/vr_render.hip | vanrijn_amd/csrc/vr_query.hip] [extra hipcc flags]
 With no source: every unit that holds a kernel of the render launch (tools/isa_sections.py device_assembly),
@@ -33,7 +33,7 @@ def report(asm):
 def report_kernel(blk):
     name = re.search(r"\.name:\s+(\S+)", blk)
     args = name and re.search(r"(?:render|query|integrate|features)_kernelIL(.*?)EEEv", name.group(1))
-    plain = name and re.search(r"\d+(denoise_\w+?_kernel)E", name.group(1))  # not a template: its own name
+    plain = name and re.search(r"\d+(denoise_\w+?_kernel|reproject_kernel)E", name.group(1))  # not a template: its own name
     if not args and not plain:
         return
     render = kernel_args(name.group(1)) if args else None

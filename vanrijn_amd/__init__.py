@@ -9,7 +9,8 @@ from .render import (AccumulationBuffer, Film, ImageRgbU8, Tile, TileIterator, p
                      query_any, query_any_device, query_closest, query_closest_device, PHOTON_DTYPE,
                      PATH_INFO_DTYPE, integrate_rays, integrate_rays_device, accumulate_photons_device,
                      camera_rays_device, FeatureBuffers, render_features, render_features_device, DenoiseParams,
-                     denoise, denoise_device, denoise_workspace_bytes)
+                     denoise, denoise_device, denoise_workspace_bytes, ReprojectParams, reproject, reproject_device,
+                     motion_rows)
 from .scene import (BoundingVolumeHierarchy, ColourRgbF, DeviceScene, DirectionalLight, LambertianMaterial,
                     MaterialSpec, Mesh, PrimitiveSpec, CameraPose, look_at, CameraLens, lens_point,
                     NamedColour, PhongMaterial, Plane, WhittedIntegrator, ReflectiveMaterial, Scene, SceneSpec, SmoothTransparentDialectric, Sphere,
@@ -25,7 +26,7 @@ __all__ = [
     "PHOTON_DTYPE", "PATH_INFO_DTYPE", "integrate_rays", "integrate_rays_device", "accumulate_photons_device",
     "camera_rays_device", "MaterialSpec", "PrimitiveSpec", "CameraPose", "look_at", "CameraLens", "lens_point",
     "load_obj_groups", "FeatureBuffers", "render_features", "render_features_device", "DenoiseParams", "denoise",
-    "denoise_device", "denoise_workspace_bytes",
+    "denoise_device", "denoise_workspace_bytes", "ReprojectParams", "reproject", "reproject_device", "motion_rows",
 ]
 
 

@@ -187,6 +187,15 @@ class DenoiseParams(C.Structure):
                 ("sigma_colour", C.c_double), ("sigma_normal", C.c_double), ("sigma_depth", C.c_double)]
 
 
+REPROJECT_MATCH_OBJECT = 1
+
+
+class ReprojectParams(C.Structure):
+    _fields_ = [("width", C.c_uint64), ("height", C.c_uint64), ("pose", CameraPose), ("previous_pose", CameraPose),
+                ("depth_tolerance", C.c_double), ("normal_tolerance", C.c_double), ("max_history_weight", C.c_double),
+                ("flags", C.c_uint32), ("motion_count", C.c_uint32)]
+
+
 # every function declared in include/vanrijn_amd.h: name -> (restype, argtypes)
 _p, _u32, _u64, _i32, _d = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32, C.c_double
 SIGNATURES = {
@@ -245,6 +254,11 @@ SIGNATURES = {
     "vr_denoise_stage_device": (C.c_int, [C.POINTER(DenoiseParams), _u32, _p, _p, _p, _p, _p, _i32, _p]),
     "vr_denoise": (C.c_int, [C.POINTER(DenoiseParams), _p, _p, _p, _p, _i32]),
     "vr_denoise_host": (C.c_int, [C.POINTER(DenoiseParams), _p, _p, _p, _p]),
+    "vr_reproject_default_params": (C.c_int, [_u64, _u64, C.POINTER(CameraPose), C.POINTER(CameraPose),
+                                              C.POINTER(ReprojectParams)]),
+    "vr_reproject_device": (C.c_int, [C.POINTER(ReprojectParams), _p, _p, _p, _p, _p, _p, _i32, _p]),
+    "vr_reproject": (C.c_int, [C.POINTER(ReprojectParams), _p, _p, _p, _p, _p, _p, _i32]),
+    "vr_reproject_host": (C.c_int, [C.POINTER(ReprojectParams), _p, _p, _p, _p, _p, _p]),
     "vr_spectrum_reflection_from_linear_rgb": (C.c_int, [_d, _d, _d, _p]),
     "vr_spectrum_intensity_at_wavelength": (_d, [C.POINTER(Spectrum), _d]),
     "vr_colour_xyz_for_wavelength": (None, [_d, _p]),

@@ -20,7 +20,7 @@ LIB = os.path.join(LIB_DIR, "libvanrijn_amd.so")
 # takes seconds, so they come first (the lens mode's, which has the most code, at the head)
 RENDER_SOURCES = ["vr_render_cam2.hip", "vr_render_cam1.hip", "vr_render_cam0.hip"]
 SOURCES = RENDER_SOURCES + [
-    "vr_denoise.hip", "vr_host_denoise.cpp", "vr_features.hip", "vr_render_launch.hip", "vr_reduce.hip", "vr_cull.hip", "vr_query.hip", "vr_integrate.hip", "vr_image.hip",
+    "vr_reproject.hip", "vr_host_reproject.cpp", "vr_denoise.hip", "vr_host_denoise.cpp", "vr_features.hip", "vr_render_launch.hip", "vr_reduce.hip", "vr_cull.hip", "vr_query.hip", "vr_integrate.hip", "vr_image.hip",
     "vr_build.hip", "vr_refit.hip", "vr_host.cpp", "vr_host_bvh.cpp", "vr_host_scene.cpp", "vr_host_edit.cpp", "vr_host_rays.cpp",
     "vr_host_film.cpp", "vr_host_io.cpp"]
 # compilers at a time: a unit compiles on one core, and a machine may report more cores than a job may use

@@ -31,6 +31,23 @@ inline const char* tuning_env(const char* name) {
 #endif
 }
 
+// what vr_scene_set_camera_pose admits (the block cull's margins are sized for these bounds): null, or why
+// not.  vr_camera_look_at and the reprojection's argument check (vr_host_reproject.cpp) share it.
+inline const char* pose_error(const vr_camera_pose& p) {
+    const vr_vec3 axes[3] = {p.right, p.up, p.forward};
+    bool finite = std::isfinite(p.location.x) && std::isfinite(p.location.y) && std::isfinite(p.location.z) &&
+                  std::isfinite(p.film_distance);
+    for (const vr_vec3& a : axes) finite = finite && std::isfinite(a.x) && std::isfinite(a.y) && std::isfinite(a.z);
+    if (!finite) return "camera pose: an entry is not finite";
+    if (!(p.film_distance >= 1e-3 && p.film_distance <= 1e3)) return "camera pose: film_distance outside [1e-3, 1e3]";
+    const auto dot = [](vr_vec3 a, vr_vec3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; };
+    for (int i = 0; i < 3; ++i) {
+        if (std::fabs(dot(axes[i], axes[i]) - 1.0) > 1e-9) return "camera pose: an axis is not of unit length (1e-9)";
+        if (std::fabs(dot(axes[i], axes[(i + 1) % 3])) > 1e-9) return "camera pose: two axes are not orthogonal (1e-9)";
+    }
+    return nullptr;
+}
+
 // host threads (vr_host_io.cpp): fn(begin, end) over [0, n) in pieces of at least `grain`; a parallel memcpy
 void parallel_range(uint64_t n, uint64_t grain, const std::function<void(uint64_t, uint64_t)>& fn);
 void parallel_copy(void* dst, const void* src, size_t bytes);

@@ -340,19 +340,7 @@ vr_vec3 normalize3(vr_vec3 a) {
     return vr_vec3{n.x, n.y, n.z};
 }
 bool film_distance_ok(double f) { return f >= 1e-3 && f <= 1e3; }  // false for a NaN
-// what vr_scene_set_camera_pose admits (the block cull's margins are sized for these bounds)
-const char* pose_error(const vr_camera_pose& p) {
-    if (!finite3(p.location) || !finite3(p.right) || !finite3(p.up) || !finite3(p.forward) ||
-        !std::isfinite(p.film_distance))
-        return "camera pose: an entry is not finite";
-    if (!film_distance_ok(p.film_distance)) return "camera pose: film_distance outside [1e-3, 1e3]";
-    const vr_vec3 axes[3] = {p.right, p.up, p.forward};
-    for (int i = 0; i < 3; ++i) {
-        if (std::fabs(dot3(axes[i], axes[i]) - 1.0) > 1e-9) return "camera pose: an axis is not of unit length (1e-9)";
-        if (std::fabs(dot3(axes[i], axes[(i + 1) % 3])) > 1e-9) return "camera pose: two axes are not orthogonal (1e-9)";
-    }
-    return nullptr;
-}
+// (what vr_scene_set_camera_pose admits: vrh::pose_error, vr_host.h)
 
 }  // namespace
 

@@ -520,6 +520,93 @@ def denoise_device(params: DenoiseParams, state_ptr, features_ptr, albedo_ptr, o
         N.check(N.lib().vr_denoise_stage_device(C.byref(params), stage, *common))
 
 
+class ReprojectParams(N.ReprojectParams):
+    """vr_reproject_params (its fields are this object's): the image size, the pose of the current frame and
+    of the frame the history was rendered from (scene.CameraPose, or the ctypes struct), the two tolerances,
+    the cap on the history's weight (math.inf: none), the flags and the number of motion rows; the library's
+    defaults where an argument is None."""
+
+    def __init__(self, width, height, pose, previous_pose, depth_tolerance=None, normal_tolerance=None,
+                 max_history_weight=None, match_object=None, motion_count=0):
+        super().__init__()
+        a, b = (p._c() if hasattr(p, "_c") else p for p in (pose, previous_pose))
+        N.check(N.lib().vr_reproject_default_params(width, height, C.byref(a), C.byref(b), C.byref(self)))
+        for name, value in (("depth_tolerance", depth_tolerance), ("normal_tolerance", normal_tolerance),
+                            ("max_history_weight", max_history_weight)):
+            if value is not None:
+                setattr(self, name, value)
+        if match_object is not None:
+            self.flags = N.REPROJECT_MATCH_OBJECT if match_object else 0
+        self.motion_count = motion_count
+
+    def __repr__(self):
+        return "ReprojectParams(%s)" % ", ".join(
+            f"{n}={getattr(self, n)!r}" for n, _ in self._fields_ if n not in ("pose", "previous_pose"))
+
+
+def motion_rows(previous_matrices, current_matrices):
+    """The `motion` rows of reproject for objects placed by transform_mesh: for each object the row-major 3x4
+    matrix M_prev * M_cur^-1, which takes a current-frame world position on the object to where that point
+    was in the previous frame.  Both arguments: [objects] matrices of 12 or 3x4 values ([A | t]); an object
+    that did not move has the same matrix in both.  Returns float64 [objects, 12]."""
+    prev = np.asarray(previous_matrices, dtype=np.float64).reshape(-1, 3, 4)
+    cur = np.asarray(current_matrices, dtype=np.float64).reshape(-1, 3, 4)
+    if prev.shape != cur.shape:
+        raise ValueError("motion_rows: as many previous as current matrices")
+    out = np.zeros((len(prev), 3, 4))
+    for i, (mp, mc) in enumerate(zip(prev, cur)):
+        if np.array_equal(mp, mc):
+            out[i] = np.eye(3, 4)  # exactly: the same-view shortcut asks for the identity entry by entry
+            continue
+        inv = np.linalg.inv(mc[:, :3])
+        out[i, :, :3] = mp[:, :3] @ inv
+        out[i, :, 3] = mp[:, 3] - out[i, :, :3] @ mc[:, 3]
+    return out.reshape(-1, 12)
+
+
+def reproject(state, features, previous_state, previous_features, params: ReprojectParams, motion=None, device=0,
+              host=False):
+    """Temporal reprojection (include/vanrijn_amd.h, "Temporal reprojection") on host arrays: the current
+    frame's flat state records and feature records (a FeatureBuffers or a record array), the history's state
+    records and the previous frame's feature records, and optionally `motion`, [rows, 12] (motion_rows).
+    Returns a new state array -- the history's contribution plus the current sums -- that resolve_state, tone
+    mapping, Film.merge_state and denoise take as it is, and that is the next call's previous_state.
+    `host`: vr_reproject_host, the same rule and bits in plain C++ with no device call; otherwise the arrays
+    are staged through the device (vr_reproject)."""
+    n = params.width * params.height
+    rec = []
+    for f in (features, previous_features):
+        f = f.records if isinstance(f, FeatureBuffers) else f
+        rec.append(np.ascontiguousarray(f, dtype=R.PIXEL_FEATURES_DTYPE))
+    st = [np.ascontiguousarray(np.asarray(s, dtype=np.float64).reshape(-1)) for s in (state, previous_state)]
+    if any(s.size != R.RECORD * n for s in st) or any(r.size != n for r in rec):
+        raise ValueError("reproject: state or features of another image size")
+    p = params
+    m = None
+    if motion is not None:
+        m = np.ascontiguousarray(np.asarray(motion, dtype=np.float64).reshape(-1, 12))
+        p = N.ReprojectParams.from_buffer_copy(params)  # the caller's params stay as they are
+        p.motion_count = len(m)
+    out = np.zeros(R.RECORD * n)
+    args = (C.byref(p), st[0].ctypes.data_as(C.c_void_p), rec[0].ctypes.data_as(C.c_void_p),
+            st[1].ctypes.data_as(C.c_void_p), rec[1].ctypes.data_as(C.c_void_p),
+            m.ctypes.data_as(C.c_void_p) if m is not None else None, out.ctypes.data_as(C.c_void_p))
+    N.check(N.lib().vr_reproject_host(*args) if host else N.lib().vr_reproject(*args, device))
+    return out
+
+
+def reproject_device(params: ReprojectParams, state_ptr, features_ptr, previous_state_ptr, previous_features_ptr, out_ptr,
+                     motion_ptr=None, stream_ptr=None, device=0):
+    """Enqueue the reprojection on device arrays on a stream, no synchronisation, no allocation and no
+    workspace (vr_reproject_device): the current state and feature records, the history's state and the
+    previous frame's feature records, the output records at `out_ptr` (may be `state_ptr`, not
+    `previous_state_ptr`) and params.motion_count rows of 12 doubles at `motion_ptr` (or None)."""
+    N.check(N.lib().vr_reproject_device(C.byref(params), C.c_void_p(state_ptr or 0), C.c_void_p(features_ptr or 0),
+                                        C.c_void_p(previous_state_ptr or 0), C.c_void_p(previous_features_ptr or 0),
+                                        C.c_void_p(motion_ptr or 0), C.c_void_p(out_ptr or 0), device,
+                                        C.c_void_p(stream_ptr or 0)))
+
+
 def render_tile_device(scene, tile: Tile, height, width, spp, seed, first_sample, state_ptr, stream_ptr=None,
                        accumulate=False, timed=False, counters=False, device=0, defer_times=False, cull=True,
                        dist_cull=True, coop=True, lone_walk=True, stack16=True, one_bvh=True):
